@@ -17,10 +17,20 @@ With a single GPU there is no peer HBM: the remote half lives in the daemon's
 pinned host tier (PCIe), like the reference's single-node coercion to host
 memory (src/alloc.c:82-83).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
 Rank 0 prints ONE JSON line. value = total bytes moved by all ranks per
-second (GiB/s) over the K timed steps, timed max-over-ranks.
+second (GiB/s) over the K timed steps, timed max-over-ranks; ms_per_step is
+the slowest rank's time per timed step.
+
+A plain run does what that line's headline needs and no more: the mesh, the
+alloc-latency samples, the pair (N>1: the kernel autotune over the links), one
+verified round trip, W warm-up steps, the K timed steps. --full adds every other
+measurement after the timed region: the per-size table, the idle-gap rows, the
+fused remote-Adam extra and, for N>1, the runtime's peer copy, the per-peer
+table and the control-plane extra (each has its own --no-* switch).
+--dump-outputs DIR writes what the last timed step left with its caller (see
+dump_outputs) as .npy files, the same bytes for the same arguments.
 """
 from __future__ import annotations
 
@@ -49,13 +59,18 @@ def parse():
     ap.add_argument("--remote", choices=["auto", "loopback", "host"], default="auto",
                     help="auto: governor placement; loopback: the rank's own daemon HBM (IPC); host: pinned host tier")
     ap.add_argument("--alloc-samples", type=int, default=200)
-    ap.add_argument("--no-characterize", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement (per-size table, idle gaps, "
+                         "fused remote-Adam, N>1: peer copy, per-peer table, control plane); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>_rank<r>.npy")
+    ap.add_argument("--no-characterize", action="store_true", help="--full: skip the per-size table and the idle gaps")
     ap.add_argument("--no-autotune", action="store_true",
                     help="N>1: skip the setup-time kernel autotune over the xGMI links (library defaults)")
-    ap.add_argument("--no-hw-baseline", action="store_true", help="skip the N>1 runtime peer-copy extras")
-    ap.add_argument("--no-optim-extra", action="store_true", help="skip the fused remote-Adam extra")
+    ap.add_argument("--no-hw-baseline", action="store_true", help="--full: skip the N>1 runtime peer-copy extras")
+    ap.add_argument("--no-optim-extra", action="store_true", help="--full: skip the fused remote-Adam extra")
     ap.add_argument("--no-ctrl-extra", action="store_true",
-                    help="N>1: skip the control-plane extra (alloc p50 with the records on TCP vs RCCL ticks)")
+                    help="--full, N>1: skip the control-plane extra (alloc p50 with the records on TCP vs RCCL ticks)")
     ap.add_argument("--daemons", choices=["embedded", "process"],
                     default=os.environ.get("OCM_BENCH_DAEMONS", "embedded"),
                     help="each rank's ocmd on a thread of the rank's process (embedded, default: one process "
@@ -145,6 +160,36 @@ def _local(fn):
         return fn(), None
     except Exception as e:  # noqa: BLE001 - recorded, never fatal
         return None, repr(e)[:200]
+
+
+# --dump-outputs: bytes sampled per job (all ranks together), 2 float32 arrays + 1 float64: 32 MiB at most
+DUMP_SAMPLES = 1 << 21
+
+
+def dump_outputs(pair, out_dir: str, rank: int, world: int, sizes, max_bytes: int) -> None:
+    """What the last timed step left with its caller: its last get filled
+    local[0:max_bytes] and its last put remote[0:max_bytes]. The remote bytes
+    come back through one more get, into the upper local half the sweep never
+    touches. Written as float32, one value per byte, at fixed offsets: every
+    byte if they fit, else a seeded sample plus both sides of every transfer
+    size's end. offsets_rank<r>.npy (float64) names them."""
+    import numpy as np
+    import torch
+
+    n = DUMP_SAMPLES // world
+    if max_bytes <= n:
+        offs = np.arange(max_bytes, dtype=np.int64)
+    else:
+        edges = [o for s in sizes for o in (s - 1, s) if o < max_bytes]
+        offs = np.unique(np.concatenate([np.random.default_rng(0).integers(0, max_bytes, n - len(edges) - 1),
+                                         np.array([0] + edges, dtype=np.int64)]))
+    pair.get(max_bytes, 0, max_bytes)
+    t = pair.local_tensor()
+    idx = torch.from_numpy(offs).to(t.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, base in (("local", 0), ("remote", max_bytes)):
+        np.save(os.path.join(out_dir, f"{name}_rank{rank}.npy"), t[idx + base].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, f"offsets_rank{rank}.npy"), offs.astype(np.float64))
 
 
 def hw_baseline_extras(dist, world: int, rank: int, local_rank: int) -> dict:
@@ -602,6 +647,8 @@ def main() -> int:
             return time.perf_counter() - t0, moved
 
         elapsed, moved = ph.run("timed", timed)
+        if args.dump_outputs:
+            ph.run("dump_outputs", lambda: dump_outputs(pair, args.dump_outputs, rank, world, sizes, max_bytes))
 
         # Self-diagnosis of the data path, per rank: peer access, IPC imports of
         # other GPUs' HBM, and the transport that carried this rank's control records.
@@ -624,7 +671,7 @@ def main() -> int:
         total = sum(s["moved"] for s in stats)
 
         sweep = {}
-        if not args.no_characterize:
+        if args.full and not args.no_characterize:
             ch = ph.run("characterize", lambda: wl.characterize(pair, sizes, breakdown_max=(4 << 20) if use_gpu else 0))
             chs = gather_obj(dist, ch, world)
             for s in sizes:
@@ -646,7 +693,7 @@ def main() -> int:
                     sweep[str(s)]["service_rank0"] = chs[0][s]["service"]
         # ---- small ops after host idle gaps: every rank at once ----
         idle_gap = {}
-        if not args.no_characterize:
+        if args.full and not args.no_characterize:
             ig = ph.run("idle_gap", lambda: wl.idle_gap_latency(pair, 4096))
             igs = gather_obj(dist, ig, world)
             idle_gap.update(wl.merge_idle_gap_rows(igs))
@@ -673,17 +720,17 @@ def main() -> int:
             if base and "1000" in idle_gap:
                 idle_gap["ratio_1ms_vs_back_to_back"] = {
                     k: round(idle_gap["1000"][f"{k}_p50_us"] / base[f"{k}_p50_us"], 2) for k in ("get", "put")}
-        # ---- extras, after the timed region (never affect the metric) ----
+        # ---- extras (--full), after the timed region (never affect the metric) ----
         # Every rank reaches every collective below even when its local part
         # fails, so a failure is recorded instead of deadlocking the job.
         optim = {}
-        if use_gpu and not args.no_optim_extra:
+        if args.full and use_gpu and not args.no_optim_extra:
             optim = optim_extra(client, dist, world, local_rank)
         baseline = {}
-        if use_gpu and world > 1 and not args.no_hw_baseline:
+        if args.full and use_gpu and world > 1 and not args.no_hw_baseline:
             baseline = hw_baseline_extras(dist, world, rank, local_rank)
         peers = {}
-        if world > 1:
+        if args.full and world > 1:
             # every rank is done with the sweep pair's owners before rank 0 loads one link at a time
             gather_obj(dist, None, world)
             peers = peer_table(client, use_gpu, world, rank, local_rank, min(256 << 20, max_bytes))
@@ -726,6 +773,7 @@ def main() -> int:
                 "app_pin": os.environ.get("OCM_PIN", "") if use_gpu else "",
                 "prearm": os.environ.get("OCM_SERVICE_PREARM", "0") if use_gpu else "",
                 "daemons": args.daemons,
+                "full": args.full,
             },
             "alloc_p50_us": round(max(s["lat"]["alloc_p50_us"] for s in stats), 2),
             "alloc_p99_us": round(max(s["lat"]["alloc_p99_us"] for s in stats), 2),
@@ -755,7 +803,7 @@ def main() -> int:
             result["hw_baseline"] = baseline
         if peers:
             result["peers_from_rank0"] = peers
-        if world > 1 and not args.no_ctrl_extra:
+        if args.full and world > 1 and not args.no_ctrl_extra:
             # needs this process's library detached from the sweep's mesh first
             _local(client.close)
             client = None

@@ -27,6 +27,69 @@ def test_bench_single(native):
     assert res["alloc_p50_us"] > 0 and res["config"]["remote_tier"] == "host"
 
 
+def _pattern_bytes(seed, nbytes):
+    """The library's word pattern (what Allocation.fill writes), computed on the host."""
+    import ctypes
+
+    import numpy as np
+
+    from oncilla_amd import api
+
+    buf = np.zeros(nbytes, dtype=np.uint8)
+    assert api.load().ocm_x_pattern(ctypes.c_void_p(buf.ctypes.data), nbytes // 4, 0, seed, 0) == 0
+    return buf
+
+
+def _bench_dump(out_dir, max_bytes, device_args, extra=()):
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), *device_args, "--steps", "2", "--warmup", "1",
+                        "--max-bytes", str(max_bytes), "--alloc-samples", "10", "--dump-outputs", str(out_dir), *extra],
+                       capture_output=True, text=True, timeout=300, cwd="/tmp")
+    assert r.returncode == 0, r.stderr[-4000:]
+    return _last_json(r.stdout)
+
+
+def check_dump(out_dir, max_bytes, res):
+    """--dump-outputs of a 1-rank run: float32 .npy files within 64 MB, the last get's and
+    the last put's bytes at the recorded offsets, both equal to the pattern the bench
+    filled the pair with (seed 1234 + rank)."""
+    import numpy as np
+
+    files = sorted(os.listdir(out_dir))
+    assert files == ["local_rank0.npy", "offsets_rank0.npy", "remote_rank0.npy"], files
+    assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in files) <= 64_000_000
+    arrs = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in files}
+    assert arrs["local_rank0"].dtype == arrs["remote_rank0"].dtype == np.float32
+    assert arrs["offsets_rank0"].dtype == np.float64
+    offs = arrs["offsets_rank0"].astype(np.int64)
+    assert 0 < len(offs) <= 1 << 21 and offs[0] == 0 and offs[-1] < max_bytes and np.all(np.diff(offs) > 0)
+    want = _pattern_bytes(1234, max_bytes)[offs].astype(np.float32)
+    assert np.array_equal(arrs["local_rank0"], want) and np.array_equal(arrs["remote_rank0"], want)
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    return arrs
+
+
+def test_bench_dump_outputs_and_plain_run(native, tmp_path):
+    """A plain run times its steps and stops: none of the --full measurements in its line.
+    --dump-outputs writes the same arrays on every run with the same arguments (every byte
+    at 1 MiB; a seeded sample with every size's end at 4 MiB), --full or not."""
+    import numpy as np
+
+    a = _bench_dump(tmp_path / "a", 1 << 20, ["--device", "cpu"])
+    assert KEYS <= set(a) and a["value"] > 0 and a["sweep"] == {} and "idle_gap_4k" not in a, a
+    assert a["config"]["full"] is False
+    arrs = check_dump(tmp_path / "a", 1 << 20, a)
+    assert len(arrs["offsets_rank0"]) == 1 << 20
+    b = _bench_dump(tmp_path / "b", 4 << 20, ["--device", "cpu"])
+    c = _bench_dump(tmp_path / "c", 4 << 20, ["--device", "cpu"], extra=["--full"])
+    assert b["sweep"] == {} and c["config"]["full"] is True
+    assert sorted(c["sweep"]) == sorted(str(4096 << k) for k in range(11)) and "idle_gap_4k" in c, c
+    arrs_b, arrs_c = check_dump(tmp_path / "b", 4 << 20, b), check_dump(tmp_path / "c", 4 << 20, c)
+    offs = set(arrs_b["offsets_rank0"].astype(np.int64).tolist())
+    assert len(offs) < 4 << 20 and {0, 4095, 4096, (2 << 20) - 1, 2 << 20, (4 << 20) - 1} <= offs
+    for k in arrs_b:
+        assert np.array_equal(arrs_b[k], arrs_c[k]), k
+
+
 # "ticks": the main mesh's records ride tick collectives as they would over RCCL on a
 # GPU node (--ctrl auto with the socket stand-in), device-sealed and queued 4 at a time
 TICK_ENV = {"OCM_CTRL_AUTO_SOCKET": "1", "OCM_TICK_SOCKET_SEAL": "1", "OCM_TICK_SOCKET_BATCH": "4"}
@@ -43,8 +106,8 @@ def test_bench_multi_rank(native, n, mode):
                         "--master-addr", "127.0.0.1", "--master-port", str(29533 + n + {"tcp": 0, "ticks": 1, "embedded": 2}[mode]),
                         os.path.join(REPO, "bench.py"),
                         "--gpus", str(n), "--device", "cpu", "--steps", "2", "--warmup", "1", "--max-bytes",
-                        str(4 << 20), "--alloc-samples", "20"], capture_output=True, text=True, timeout=300, cwd="/tmp",
-                       env=env)
+                        str(4 << 20), "--alloc-samples", "20", "--full"], capture_output=True, text=True, timeout=300,
+                       cwd="/tmp", env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-8000:]  # the ranks' tracebacks precede torchrun's summary
     res = _last_json(r.stdout)
     assert res["n_gpus"] == n and res["value"] > 0 and res["config"]["parallelism"] == f"stripe{n}"

@@ -202,7 +202,7 @@ def test_bench_on_real_gpus():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(k),
                         "--master-addr", "127.0.0.1", "--master-port", "29671", os.path.join(repo, "bench.py"),
                         "--gpus", str(k), "--steps", "1", "--warmup", "1", "--max-bytes", str(1 << 30),
-                        "--alloc-samples", "50", "--no-characterize"],
+                        "--alloc-samples", "50", "--full", "--no-characterize"],
                        capture_output=True, text=True, timeout=900, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-4000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -103,11 +103,23 @@ def test_graft_smoke():
 
 def test_bench_gpu_small():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--max-bytes",
-                        str(64 << 20), "--alloc-samples", "50"], capture_output=True, text=True, timeout=600,
+                        str(64 << 20), "--alloc-samples", "50", "--full"], capture_output=True, text=True, timeout=600,
                        cwd="/tmp")
     assert r.returncode == 0, r.stderr[-4000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert res["config"]["device"] == "gpu" and res["value"] > 0
+
+
+def test_bench_gpu_dump_outputs(native, tmp_path):
+    """--dump-outputs on the GPU: the last step's get and put results (service, gang and
+    launch paths up to 32 MiB through the host tier), sampled, equal the fill pattern;
+    and the plain run it rides on carries none of the --full measurements."""
+    from test_bench_cpu import _bench_dump, check_dump
+
+    res = _bench_dump(tmp_path / "out", 32 << 20, [])
+    assert res["config"]["device"] == "gpu" and res["value"] > 0 and res["sweep"] == {}, res
+    assert "fused_remote_adam" not in res and "idle_gap_4k" not in res, res
+    check_dump(tmp_path / "out", 32 << 20, res)
 
 
 def test_bench_two_ranks_sharing_one_gpu():
@@ -118,7 +130,7 @@ def test_bench_two_ranks_sharing_one_gpu():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29641", os.path.join(REPO, "bench.py"),
                         "--gpus", "2", "--steps", "1", "--warmup", "1", "--max-bytes", str(32 << 20),
-                        "--alloc-samples", "50", "--no-characterize", "--no-hw-baseline"],
+                        "--alloc-samples", "50", "--full", "--no-characterize", "--no-hw-baseline"],
                        capture_output=True, text=True, timeout=300, cwd="/tmp", env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

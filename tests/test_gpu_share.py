@@ -27,7 +27,7 @@ def test_shared_gpu_rehearsal_is_clean(daemons):
         p = subprocess.Popen([sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
                               "4", "--master-addr", "127.0.0.1", "--master-port", "29681",
                               os.path.join(REPO, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                              "--max-bytes", str(64 << 20), "--alloc-samples", "50", "--no-ctrl-extra",
+                              "--max-bytes", str(64 << 20), "--alloc-samples", "50", "--full", "--no-ctrl-extra",
                               "--no-hw-baseline", "--no-optim-extra"],
                              stdout=lf, stderr=subprocess.STDOUT, text=True, cwd="/tmp", env=env,
                              start_new_session=True)

@@ -66,7 +66,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nproc", type=int, default=2)
     ap.add_argument("--share", action="store_true", help="every rank on GPU 0 (OCM_BENCH_SHARE_GPU=1)")
-    ap.add_argument("--bench-args", default="--steps 2 --warmup 1")
+    ap.add_argument("--bench-args", default="--full --steps 2 --warmup 1")
     ap.add_argument("--timeout", type=float, default=900)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
