@@ -10,7 +10,7 @@
 // against 2.2 us for hipLaunchKernelGGL (profiles/hsa_dispatch_probe_r04.json).
 //
 // The kernels come from a gfx950 device code object embedded in libocm at build
-// time (the same xfer.hip source the HIP fat binary is built from), loaded into
+// time (the same xfer_service.hip source the HIP fat binary is built from), loaded into
 // an HSA executable for the agent whose PCI location matches the HIP device.
 #pragma once
 #include <cstddef>

@@ -62,6 +62,18 @@ struct XferDone {
     unsigned long long val = 0;
 };
 
+// Tiles (aligned to 1 << tile_shift in striped coordinates) that [rem_off, rem_off + len)
+// touches, and the start of the first one. Host and device size grids, gangs and batch
+// plans with this one expression: a disagreement would size a gang for tiles that no
+// member copies. Callers guard len == 0 themselves (at an unaligned offset it yields 1).
+__host__ __device__ inline uint64_t xfer_first_tile(uint64_t rem_off, uint32_t tile_shift) {
+    return rem_off & ~((1ull << tile_shift) - 1);
+}
+__host__ __device__ inline uint64_t xfer_tile_count(uint64_t rem_off, uint64_t len, uint32_t tile_shift) {
+    const uint64_t mask = (1ull << tile_shift) - 1;
+    return (((rem_off + len + mask) & ~mask) - (rem_off & ~mask)) >> tile_shift;
+}
+
 // Validate and fill tile_shift (xfer_launch does this itself; the service needs it up front).
 hipError_t xfer_normalize(XferArgs &a);
 
@@ -108,7 +120,7 @@ struct XferBatchArgs {
     uint64_t total_tiles;
     uint32_t grid;                        // workgroups (4 waves each)
     uint32_t abs_lin;                     // 1: op.lin_off is an absolute device address (lin unused)
-    uint32_t host_tier;                   // 1: every extent is pinned host memory (PCIe launch shape, sc1 puts)
+    uint32_t host_tier;                   // 1: every extent is pinned host memory (PCIe launch shape)
     uint32_t pad0;
     const XferBatchOp *ops;               // device copy when n_ops > kXferInlineOps
     const uint32_t *wave_op;              // device: first op of each wave (n_ops > kXferInlineOps)

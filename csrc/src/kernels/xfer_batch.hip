@@ -1,0 +1,134 @@
+// Batched one-sided ops (scatter/gather lists) as one launch of wave-granular
+// copies; see ocm/xfer.h for the plan the host makes and the kernel walks.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "ocm/xfer.h"
+#include "xfer_copy.h"
+#include "xfer_host.h"
+
+namespace ocm {
+
+namespace {
+
+constexpr uint32_t kBatchTileShift = 12;  // 4 KiB per wave-tile: 64 lanes x 16 B x 4 in flight
+constexpr int kBatchUnroll = 4;
+
+// One wave copies a span (n <= one wave-tile in the common case; any n works)
+// through pointers, with plain or nontemporal (NT) stores.
+template <bool NT>
+using WaveCopy = CopyCfg<64, kBatchUnroll, PointerAccess<NT>>;
+
+// HOST: the host-tier shape. Its puts were meant to store write-through (sc1) into
+// the pinned host extents, as the PCIe streaming kernel does (57.0 vs 55.5 GB/s),
+// but pointer stores carry no sc1 bit: they are plain stores, whatever NT says.
+// (Making them write-through is an open measurement: docs/DESIGN.md.)
+template <bool NT, bool HOST = false>
+__global__ __launch_bounds__(kThreads) void xfer_batch_kernel(XferBatchArgs a) {
+    // wave index, made scalar: everything below is wave-uniform
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
+    const uint64_t waves = (uint64_t)a.grid * kWaves;
+    const uint64_t per = (a.total_tiles + waves - 1) / waves;
+    uint64_t t = (uint64_t)w * per;
+    const uint64_t t1 = t + per < a.total_tiles ? t + per : a.total_tiles;
+    if (t >= t1) return;
+    const bool inl = a.n_ops <= (uint32_t)kXferInlineOps;
+    const XferBatchOp *ops = inl ? a.inline_ops : a.ops;
+    uint32_t i = inl ? 0u : a.wave_op[w];
+    for (; t < t1; t++) {
+        while (i + 1 < a.n_ops && ops[i + 1].first_tile <= t) i++;
+        const XferBatchOp &op = ops[i];
+        char *lin = a.abs_lin ? reinterpret_cast<char *>(static_cast<uintptr_t>(op.lin_off)) : a.lin + op.lin_off;
+        TileSpan sp = tile_span_of(a, a.n_ext, a.unit_shift, a.tile_shift, lin, op.rem_off, op.len, op.put,
+                                   t - op.first_tile, xfer_first_tile(op.rem_off, a.tile_shift));
+        if (HOST && op.put)
+            copy_span<WaveCopy<false>>(sp.dst, sp.src, sp.n);
+        else
+            copy_span<WaveCopy<NT>>(sp.dst, sp.src, sp.n);
+    }
+}
+
+// The host-tier kernel for host-tier batches (OCM_BATCH_HOST_SC1=0: the generic kernel).
+bool host_sc1() {
+    static const bool on = kernels::env_int("OCM_BATCH_HOST_SC1", 1) != 0;
+    return on;
+}
+
+using BatchKernel = void (*)(XferBatchArgs);
+
+BatchKernel batch_kernel_for(const XferBatchArgs &a, const XferTuning &t) {
+    if (a.host_tier && host_sc1()) return xfer_batch_kernel<true, true>;
+    return t.nontemporal ? xfer_batch_kernel<true> : xfer_batch_kernel<false>;
+}
+
+// Whether a batch with something to copy can be launched.
+bool batch_args_valid(const XferBatchArgs &a) {
+    if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || a.grid == 0) return false;
+    return a.n_ops <= (uint32_t)kXferInlineOps || (a.ops && a.wave_op);
+}
+
+}  // namespace
+
+uint32_t xfer_batch_tile_shift(uint32_t n_ext, uint32_t unit_shift) {
+    return (n_ext > 1 && unit_shift < kBatchTileShift) ? unit_shift : kBatchTileShift;
+}
+
+uint64_t xfer_batch_plan(XferBatchOp *ops, uint32_t n, uint32_t tile_shift) {
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        ops[i].first_tile = total;
+        if (ops[i].len) total += xfer_tile_count(ops[i].rem_off, ops[i].len, tile_shift);
+    }
+    return total;
+}
+
+uint32_t xfer_batch_grid(uint64_t total_tiles, bool host_tier) {
+    // One wave per tile until the chip holds 8 workgroups (32 waves) per CU.
+    const uint64_t want = (total_tiles + kWaves - 1) / kWaves;
+    // Host tier: 128 workgroups; 4096-block KV swaps 48.0-48.1 /
+    // 48.8-49.9 GiB/s out/in against 46.8-46.9 / 47.5-48.1 with the HBM shape
+    // (profiles/kv_swap_host_r03.json; the PCIe ceiling is ~53).
+    static const int host_grid = kernels::env_int("OCM_BATCH_HOST_GRID", 128);
+    const uint64_t cap = host_tier && host_grid > 0 ? (uint64_t)host_grid : (uint64_t)kernels::num_cus() * 8;
+    return (uint32_t)(want < cap ? (want ? want : 1) : cap);
+}
+
+void xfer_batch_wave_ops(const XferBatchOp *ops, uint32_t n, uint64_t total_tiles, uint32_t grid, uint32_t *out) {
+    const uint64_t waves = (uint64_t)grid * kWaves;
+    const uint64_t per = (total_tiles + waves - 1) / waves;
+    uint32_t i = 0;
+    for (uint64_t w = 0; w < waves; w++) {
+        const uint64_t t = w * per;
+        while (i + 1 < n && ops[i + 1].first_tile <= t) i++;
+        out[w] = i;
+    }
+}
+
+hipError_t xfer_batch_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream) {
+    if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
+    if (!batch_args_valid(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(batch_kernel_for(a, t), dim3(a.grid), dim3(kThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t xfer_batch_graph_node(hipGraph_t graph, hipGraphNode_t dep, const XferBatchArgs &a, const XferTuning &t,
+                                 hipGraphNode_t *node) {
+    const size_t ndep = dep ? 1 : 0;
+    if (a.total_tiles == 0 || a.n_ops == 0) return hipGraphAddEmptyNode(node, graph, dep ? &dep : nullptr, ndep);
+    if (!batch_args_valid(a)) return hipErrorInvalidValue;
+    // Parameters by address: `a` must outlive the graph (the plan's stage
+    // storage), whether or not the runtime copies them into the node.
+    void *params[] = {const_cast<XferBatchArgs *>(&a)};
+    hipKernelNodeParams kp;
+    std::memset(&kp, 0, sizeof(kp));
+    kp.func = reinterpret_cast<void *>(batch_kernel_for(a, t));
+    kp.gridDim = dim3(a.grid);
+    kp.blockDim = dim3(kThreads);
+    kp.sharedMemBytes = 0;
+    kp.kernelParams = params;
+    kp.extra = nullptr;
+    return hipGraphAddKernelNode(node, graph, dep ? &dep : nullptr, ndep, &kp);
+}
+
+}  // namespace ocm

@@ -14,7 +14,7 @@
 
 #include "ocm/log.h"
 
-// The gfx950 device code object of xfer.hip, embedded by the build (aql_devcode.S).
+// The gfx950 device code object of xfer_service.hip, embedded by the build (aql_devcode.S).
 extern "C" const char ocm_devcode_begin[];
 extern "C" const char ocm_devcode_end[];
 

@@ -27,6 +27,7 @@
 #include "ocm/shmlink.h"
 #include "ocm/siphash.h"
 #include "ocm/tick.h"
+#include "ocm/xfer.h"
 
 using namespace ocm;
 
@@ -366,6 +367,33 @@ static void t_stripe_geometry() {
     CHECK(stripe_extent_bytes(10000, 4096, 2, 1) == 4096);
 }
 
+// xfer_tile_count / xfer_first_tile (and the gang size built on them) against a
+// brute-force count of the distinct tiles that [rem_off, rem_off + len) touches.
+static void t_tile_count() {
+    for (uint32_t shift : {4u, 12u, 13u, 15u}) {
+        const uint64_t T = 1ull << shift;
+        for (uint64_t rem_off : {uint64_t(0), uint64_t(1), T - 1, T, T + 1, 5 * T + 3}) {
+            for (uint64_t len : {uint64_t(1), T - 1, T, T + 1, 3 * T + 5}) {
+                std::set<uint64_t> tiles;
+                for (uint64_t o = rem_off; o < rem_off + len; o++) tiles.insert(o >> shift);
+                CHECK(xfer_tile_count(rem_off, len, shift) == tiles.size());
+                CHECK(xfer_first_tile(rem_off, shift) == *tiles.begin() << shift);
+                XferArgs a;
+                std::memset(&a, 0, sizeof(a));
+                a.rem_off = rem_off;
+                a.len = len;
+                a.tile_shift = shift;
+                for (unsigned blocks : {1u, 2u, 128u}) {
+                    for (unsigned solo : {0u, 2u}) {
+                        const uint64_t want = (blocks <= 1 || tiles.size() <= solo) ? 1 : std::min<uint64_t>(tiles.size(), blocks);
+                        CHECK(service_gang_size(a, blocks, solo) == want);
+                    }
+                }
+            }
+        }
+    }
+}
+
 static void t_arena_host() {
     ArenaConfig ac;
     ac.gpu = -1;
@@ -645,6 +673,7 @@ int main(int argc, char **argv) {
                  {"governor_checkpoint", t_governor_checkpoint},
                  {"governor_replica", t_governor_replica},
                  {"stripe_geometry", t_stripe_geometry},
+                 {"tile_count", t_tile_count},
                  {"arena_host", t_arena_host},   {"siphash", t_siphash},
                  {"shmlink", t_shmlink},         {"tick_tags", t_tick_tags},
                  {"tick_transport", t_tick_transport},

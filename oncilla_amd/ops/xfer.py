@@ -2,7 +2,7 @@
 
 Used by the numerics tests (kernel vs a plain PyTorch reference of the same
 copy) and by the kernel micro-benchmarks. The kernels live in libocm.so
-(csrc/src/kernels/xfer.hip); this module fails loudly when it is missing.
+(csrc/src/kernels/xfer.hip, xfer_batch.hip); this module fails loudly when it is missing.
 """
 from __future__ import annotations
 

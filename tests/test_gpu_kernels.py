@@ -29,6 +29,35 @@ def test_device_copy_matches_torch(variant, n, soff, doff):
     assert torch.equal(dst, ref)
 
 
+# tile of each copier: the sizes below straddle it
+_COPIER_TILE = {"reg": 32768, "lds": 32768, "pcie": 8192, "push": 32768, "batch": 4096}
+_COPIER_VARIANT = {"reg": ops.XFER_REG, "lds": ops.XFER_LDS, "pcie": ops.XFER_PCIE, "push": ops.XFER_PUSH}
+
+
+@pytest.mark.parametrize("soff,doff", [(0, 0), (5, 5), (5, 9), (0, 1)])
+@pytest.mark.parametrize("path", ["reg", "lds", "pcie", "push", "batch"])
+def test_copier_alignment_matrix_keeps_guards(path, soff, doff):
+    # Every copier over (source, destination) offsets mod 16 - aligned, equal, unequal - and
+    # sizes around 16 bytes and around its tile: byte-exact against a torch slice copy, with
+    # 64 guard bytes before and after the destination range untouched.
+    tile, guard = _COPIER_TILE[path], 64
+    for n in (1, 15, 16, 17, 31, tile - 1, tile, tile + 1, 2 * tile + 33):
+        src = _rand(soff + n, n)
+        dst = _rand(guard + doff + n + guard, n + 1)
+        assert src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
+        s, d = src[soff:], dst[guard + doff:]
+        ref = dst.clone()
+        ref[guard + doff:guard + doff + n] = src[soff:soff + n]
+        if path == "batch":
+            ops.batch(s, [d], 0, [(True, 0, 0, n)])
+        elif path == "push":  # a get: the extent is the source
+            ops.xfer(d, [s], 0, 0, n, put=False, variant=ops.XFER_PUSH)
+        else:
+            ops.xfer(s, [d], 0, 0, n, put=True, variant=_COPIER_VARIANT[path])
+        torch.cuda.synchronize()
+        assert torch.equal(dst, ref), (path, n, soff, doff)
+
+
 @pytest.mark.parametrize("variant", [ops.XFER_REG, ops.XFER_LDS, ops.XFER_PCIE])
 @pytest.mark.parametrize("n_ext,unit", [(2, 4096), (3, 65536), (7, 1 << 20), (8, 32768)])
 @pytest.mark.parametrize("put", [True, False])

@@ -476,14 +476,19 @@ def test_copy_service_protocols(mesh_factory, monkeypatch, proto):
         n = 1 << 20
         a = c.alloc(api.OCM_REMOTE_GPU, local_bytes=n, remote_bytes=n)
         before = api.service_stats()["ops"]
-        for i, (size, off) in enumerate([(4096, 0), (100, 4), (65536 + 12, 4096), (256 << 10, 1 << 16)]):
+        # (size, local offset, remote offset). The last four touch exactly two 32 KiB tiles, which
+        # one workgroup copies with both tiles' loads in flight: whole and with a byte tail, offsets
+        # equal mod 16 (vector rounds) and unequal (the one-after-the-other byte copy).
+        cases = [(4096, 0, 0), (100, 4, 4), (65536 + 12, 4096, 4096), (256 << 10, 1 << 16, 1 << 16),
+                 (65536, 16, 32768), (65536, 4, 32768), (65536 - 7, 4, 32768 + 4), (65536 - 7, 8, 32768 + 4)]
+        for i, (size, off, roff) in enumerate(cases):
             a.fill(seed=40 + i)
-            a.put(off, off, size)
+            a.put(off, roff, size)
             a.fill(seed=0)
-            a.get(off, off, size)
-            assert a.check(seed=40 + i, offset=off, nbytes=size - size % 4, first_word=off // 4) == 0, (size, off)
+            a.get(off, roff, size)
+            assert a.check(seed=40 + i, offset=off, nbytes=size - size % 4, first_word=off // 4) == 0, (size, off, roff)
         st = api.service_stats()
-        assert st["ops"] - before == 8, st
+        assert st["ops"] - before == 2 * len(cases), st
         assert st["relaunches"] >= 0, st
         assert st["gpu_us"] is not None and 0 < st["gpu_us"] < 1000, st
         a.free()

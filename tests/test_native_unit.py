@@ -25,7 +25,8 @@ def test_abi_layout(native):
             api.OCM_LOCAL_GPU, api.OCM_REMOTE_GPU) == tuple(range(1, 8))
 
 
-@pytest.mark.parametrize("src,min_kernels", [("xfer.hip", 9), ("optim.hip", 1)])
+@pytest.mark.parametrize("src,min_kernels", [("xfer.hip", 8), ("xfer_batch.hip", 3), ("xfer_service.hip", 2),
+                                             ("xfer_pattern.hip", 2), ("optim.hip", 1)])
 def test_kernels_use_no_scratch(src, min_kernels):
     # Resource check of every gfx950 kernel: a dynamically indexed local array
     # (e.g. a copied extent table) lands in scratch and costs a memory round
@@ -79,6 +80,8 @@ def test_embedded_service_code_object_layout(native):
     assert "amdgcn-amd-amdhsa--gfx950" in notes
     kern = [k for k in re.split(r"\n  - ", notes) if re.search(r"\.name:\s+ocm_service_kernel\s", k)]
     assert len(kern) == 1, "ocm_service_kernel missing from the embedded code object"
+    # the service's two kernels and nothing else (the unit that holds them is compiled alone)
+    assert sorted(re.findall(r"\.name:\s+(\S+)", notes)) == ["ocm_service_box_clear", "ocm_service_kernel"]
     args = {kind: (int(off), int(size)) for off, size, kind in
             re.findall(r"\.offset:\s+(\d+)\s+\.size:\s+(\d+)\s+\.value_kind:\s+(\S+)", kern[0])}
     assert args["by_value"] == (0, 216), args

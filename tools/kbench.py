@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Transfer-kernel micro-benchmark on one MI355X.
 
-Measures the gfx950 put/get kernel (csrc/src/kernels/xfer.hip) against the
+Measures the gfx950 put/get kernel (csrc/src/kernels/xfer.hip, copy loop in xfer_copy.h) against the
 vendor paths on the same buffers:
   hbm      HBM -> HBM copy: xfer REG/LDS (grid sweep, nt on/off) vs torch copy_ (blit)
   d2h/h2d  device <-> pinned host: xfer kernel through the mapped pointer vs

@@ -1,7 +1,7 @@
 // Probe: how fast can G workgroups move S bytes between HBM and registered host
 // memory (the host tier) over PCIe, as seen on the GPU clock?
 //
-// The copy service (csrc/src/kernels/xfer.hip) copies 32 KiB tiles with 8 x 16 B
+// The copy service (csrc/src/kernels/xfer_service.hip, copy loop in xfer_copy.h) copies 32 KiB tiles with 8 x 16 B
 // loads then 8 x 16 B stores per lane. On gfx9-family parts vmcnt counts loads AND
 // stores in issue order, so the loads of tile k+1 wait for the stores of tile k:
 // over PCIe every tile costs a full write (put) or read (get) round trip. This
