@@ -1,0 +1,27 @@
+// Converting one-sided ops (ocm_copy_onesided_quant): a put reads 16-bit elements
+// from the linear side and writes an MXFP8 record (ocm/mx8.h) into the striped
+// side, a get reads the record and widens it. One launch serves a whole list,
+// planned like a batch (ocm/xfer.h): the list is cut into wave-tiles of
+// kQuantTileElems elements, the host prefix-sums each op's tile count into
+// `first_tile`, and every wave walks a contiguous tile range.
+//
+// The descriptors are XferBatchOp records read differently: len counts elements,
+// rem_off is the record's first byte (codes, then the scale bytes), pad holds the
+// element type (enum ocm_quant_dtype). XferBatchArgs carries them unchanged
+// (tile_shift is unused), so large lists take the batch path's staged upload.
+#pragma once
+#include "ocm/xfer.h"
+
+namespace ocm {
+
+constexpr uint32_t kQuantTileShift = 11;  // 2048 elements: 4 KiB of source, 2 KiB of codes, 64 scale bytes
+constexpr uint32_t kQuantTileElems = 1u << kQuantTileShift;
+
+// Fills first_tile, returns total tiles.
+uint64_t xfer_quant_plan(XferBatchOp *ops, uint32_t n);
+// a.grid from xfer_batch_grid, a.wave_op from xfer_batch_wave_ops (large lists).
+// Stores: nontemporal (t.nontemporal), except that puts into a pool wholly in the
+// pinned host tier (a.host_tier) store plain, as the batch kernel's host shape does.
+hipError_t xfer_quant_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream);
+
+}  // namespace ocm

@@ -15,6 +15,8 @@ struct OpCounters {
     uint64_t ns_put = 0, ns_get = 0, ns_alloc = 0, ns_free = 0;
     uint64_t n_batch = 0, n_batch_ops = 0, bytes_batch = 0, ns_batch = 0;
     uint64_t n_batch_launches = 0;  // batch kernels launched outside plans (batches, remote->remote copies)
+    // converting ops (ocm_copy_onesided_quant): calls, ops, 16-bit source bytes, record bytes on the wire
+    uint64_t n_quant = 0, n_quant_ops = 0, bytes_quant_src = 0, bytes_quant_wire = 0;
     uint64_t n_slab_fd = 0;         // host-tier slabs imported through an fd from their owner (SCM_RIGHTS)
     uint64_t n_slab_path = 0;       // ... through the /proc/<pid>/fd path fallback
     uint64_t n_link_rpc = 0;        // RPCs posted on the shared-memory link (ocm/shmlink.h)

@@ -149,6 +149,29 @@ int ocm_wait(ocm_alloc_t a);
  * defined order. flags: OCM_BATCH_ASYNC completes later (ocm_wait). */
 #define OCM_BATCH_ASYNC 1
 int ocm_copy_onesided_batch(ocm_alloc_t a, const struct ocm_params *ops, int n_ops, int flags);
+/* Converting one-sided copies: the local half holds 16-bit elements, the remote half
+ * MXFP8 records, 33/64 of the bytes. A put (op_flag 1) reads `elems` elements at
+ * local_offset and writes their record at remote_offset; a get (op_flag 0) reads the
+ * record and widens it. A record is contiguous: `elems` OCP e4m3fn code bytes, then
+ * elems / 32 scale bytes, one per group of 32 consecutive elements: e + 127, where
+ * 2^e is the group's shared power-of-two scale (the smallest with
+ * max|x| * 2^-e <= 448). Decoding gives float(code) * 2^e rounded to nearest even
+ * (docs/API.md has the exact rule). Constraints per op: elems % 32 == 0 and
+ * elems < 2^31, local_offset % 16 == 0, remote_offset % 32 == 0, both ranges inside
+ * their halves. Ops of one call run concurrently, puts and gets mixed, as ONE gfx950
+ * launch when the local half is device memory; flags and ordering as for
+ * ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait, ocm_stream_wait/signal). */
+enum ocm_quant_dtype { OCM_QUANT_BF16 = 1, OCM_QUANT_FP16 = 2 };
+struct ocm_quant_params {
+    uint64_t local_offset;  /* bytes into the local half */
+    uint64_t remote_offset; /* first byte of the record in the remote half */
+    uint64_t elems;         /* 16-bit elements */
+    int32_t  op_flag;       /* 1 = put (encode), 0 = get (decode) */
+    uint32_t dtype;         /* enum ocm_quant_dtype */
+};
+/* Bytes of the record of `elems` elements: elems + elems / 32. */
+size_t ocm_quant_bytes(uint64_t elems);
+int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags);
 /* Stream interop (hipStream_t passed as void*, NULL = legacy default stream):
  * ocm_stream_wait:   a's next one-sided op starts after the work already queued on `stream`
  *                    (e.g. torch kernels that wrote the local half).

@@ -233,10 +233,22 @@ __device__ __forceinline__ void copy_span2(const TileSpan &a, const TileSpan &b)
     if ((uint64_t)lane < tb) copy_byte<AB>(b.dst + ob + lane, b.src + ob + lane);
 }
 
+// Address of byte `off` of the striped address space. `E` holds the extent bases
+// (`E::ext[]`); it is read in place (kernarg segment or LDS): copying it to a
+// local array would put the dynamically indexed array in scratch.
+template <class E>
+__device__ __forceinline__ char *stripe_ptr(const E &x, uint32_t n_ext, uint32_t unit_shift, uint64_t off) {
+    if (n_ext == 1) return x.ext[0] + off;
+    // Stripe unit u of the address space lives on extent u % n at (u / n) * unit.
+    const uint64_t unit_mask = (1ull << unit_shift) - 1;
+    const uint32_t u = (uint32_t)(off >> unit_shift);
+    const uint32_t e = u % n_ext;
+    const uint64_t eoff = ((uint64_t)(u / n_ext) << unit_shift) | (off & unit_mask);
+    return x.ext[e] + eoff;
+}
+
 // Span of tile `ti` of a transfer of [rem_off, rem_off + len) in striped
-// coordinates. `E` holds the extent bases (`E::ext[]`); it is read in place
-// (kernarg segment or LDS): copying it to a local array would put the
-// dynamically indexed array in scratch.
+// coordinates (extent bases in `x`, see stripe_ptr).
 template <class E>
 __device__ __forceinline__ TileSpan tile_span_of(const E &x, uint32_t n_ext, uint32_t unit_shift, uint32_t tile_shift,
                                                  char *lin, uint64_t rem_off, uint64_t len, uint32_t put, uint64_t ti,
@@ -246,17 +258,7 @@ __device__ __forceinline__ TileSpan tile_span_of(const E &x, uint32_t n_ext, uin
     const uint64_t lo = first_tile + (ti << tile_shift);
     const uint64_t ts = lo > r0 ? lo : r0;
     const uint64_t te = (lo + tile) < r1 ? (lo + tile) : r1;
-    char *rp;
-    if (n_ext == 1) {
-        rp = x.ext[0] + ts;
-    } else {
-        // Stripe unit u of the address space lives on extent u % n at (u / n) * unit.
-        const uint64_t unit_mask = (1ull << unit_shift) - 1;
-        const uint32_t u = (uint32_t)(ts >> unit_shift);
-        const uint32_t e = u % n_ext;
-        const uint64_t eoff = ((uint64_t)(u / n_ext) << unit_shift) | (ts & unit_mask);
-        rp = x.ext[e] + eoff;
-    }
+    char *rp = stripe_ptr(x, n_ext, unit_shift, ts);
     char *lp = lin + (ts - r0);
     TileSpan s;
     s.dst = put ? rp : lp;

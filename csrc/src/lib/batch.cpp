@@ -6,18 +6,27 @@
 using namespace ocm;
 using namespace ocmlib;
 
-// Launch geometry of a batch on `a` for the descriptors in `v` (first_tile filled in).
-static void plan_batch_args(lib_alloc *a, std::vector<XferBatchOp> &v, bool abs_lin, XferBatchArgs *args) {
+namespace ocmlib {
+
+// The pair's side of batch launch arguments: the linear base, the extents and how they stripe.
+void batch_layout_args(lib_alloc *a, bool abs_lin, XferBatchArgs *args) {
     std::memset(args, 0, sizeof(*args));
     args->lin = abs_lin ? nullptr : static_cast<char *>(a->local);
     args->abs_lin = abs_lin ? 1 : 0;
     for (size_t i = 0; i < a->ext.size(); i++) args->ext[i] = a->ext[i].dptr;
     args->n_ext = (uint32_t)a->ext.size();
     args->unit_shift = args->n_ext > 1 ? (uint32_t)log2_exact(a->stripe_unit) : 0;
+    args->host_tier = (!a->any_gpu && !a->any_net) ? 1u : 0u;
+}
+
+}  // namespace ocmlib
+
+// Launch geometry of a batch on `a` for the descriptors in `v` (first_tile filled in).
+static void plan_batch_args(lib_alloc *a, std::vector<XferBatchOp> &v, bool abs_lin, XferBatchArgs *args) {
+    batch_layout_args(a, abs_lin, args);
     args->tile_shift = xfer_batch_tile_shift(args->n_ext, args->unit_shift);
     args->n_ops = (uint32_t)v.size();
     args->total_tiles = xfer_batch_plan(v.data(), (uint32_t)v.size(), args->tile_shift);
-    args->host_tier = (!a->any_gpu && !a->any_net) ? 1u : 0u;
     args->grid = args->total_tiles ? xfer_batch_grid(args->total_tiles, args->host_tier != 0) : 0;
     if (v.size() <= (size_t)kXferInlineOps) std::memcpy(args->inline_ops, v.data(), v.size() * sizeof(XferBatchOp));
 }
@@ -50,17 +59,18 @@ static int check_batch_ops(lib_alloc *a, const struct ocm_params *ops, int n_ops
     return 0;
 }
 
+namespace ocmlib {
+
 // One kernel can serve this pair: device local half, every extent device-accessible.
-static bool batch_device_path(const lib_alloc *a) {
+bool batch_device_path(const lib_alloc *a) {
     const State &s = S();
     return s.device >= 0 && a->loc == LOC_DEVICE && a->all_dev_ok && !a->any_net &&
            (a->ext.size() == 1 || log2_exact(a->stripe_unit) >= 4);
 }
 
-namespace ocmlib {
-
-// Upload (large lists), launch and complete one batch on `a`. `args` from plan_batch_args.
-int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async) {
+// Upload (large lists), launch and complete one batch on `a`. `args` from plan_batch_args,
+// or a converting list's (quant.cpp; `quant`: the launch is xfer_quant_launch).
+int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, bool quant) {
     State &s = S();
     DeviceGuard guard(s.device);
     if (!async && wait_alloc(a) != 0) return -1;
@@ -100,9 +110,9 @@ int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bo
         args.wave_op = reinterpret_cast<const uint32_t *>(static_cast<char *>(a->batch_dev) + dbytes);
     }
     before_launch();
-    err = xfer_batch_launch(args, s.tuning, st);
+    err = quant ? xfer_quant_launch(args, s.tuning, st) : xfer_batch_launch(args, s.tuning, st);
     if (err != hipSuccess) OCM_FAIL(-1, "batch launch failed: %s", hipGetErrorString(err));
-    s.ctr.n_batch_launches++;
+    if (!quant) s.ctr.n_batch_launches++;
     if (async) {
         if (st != s.stream && a->ev) {
             err = hipEventRecord(a->ev, st);

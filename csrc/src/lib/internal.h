@@ -4,6 +4,7 @@
 // transfer.cpp copy engine: segments, lanes/events, copy service, xfer, local copies
 // net.cpp      network-tier client (owners on other nodes)
 // batch.cpp    batched one-sided ops, stream interop, transfer plans (hipGraph)
+// quant.cpp    converting one-sided ops (ocm_copy_onesided_quant: MXFP8 records)
 // libocm.cpp   the C ABI (oncillamem.h)
 #pragma once
 #include <fcntl.h>
@@ -38,6 +39,7 @@
 #include "ocm/stackdump.h"
 #include "ocm/trace.h"
 #include "ocm/aql.h"
+#include "ocm/quant.h"
 #include "ocm/xfer.h"
 
 
@@ -547,7 +549,9 @@ void push_release();
 char *extent_view(const Extent &e, int dev);
 
 // ---- batches (batch.cpp)
-int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async);
+int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, bool quant = false);
+bool batch_device_path(const lib_alloc *a);
+void batch_layout_args(lib_alloc *a, bool abs_lin, XferBatchArgs *args);
 // Copy absolute device ranges (op.lin_off = address) into dst's remote half, one launch.
 int batch_put_abs(lib_alloc *dst, std::vector<XferBatchOp> &v);
 

@@ -1,0 +1,119 @@
+// libocm converting one-sided ops (ocm_copy_onesided_quant): 16-bit elements in
+// the local half, MXFP8 records (ocm/mx8.h) in the remote half. A device local
+// half takes one kernel launch per list (ocm/quant.h), ordered like a batch; a
+// host local half (a CPU app, OCM_REMOTE_RDMA / _RMA pairs, the network tier)
+// encodes and decodes on this thread and moves each record with xfer().
+#include "internal.h"
+#include "ocm/mx8.h"
+
+using namespace ocm;
+using namespace ocmlib;
+
+// Every op against the pair and the format's constraints. Adds to *src / *wire.
+static int check_quant_ops(lib_alloc *a, const struct ocm_quant_params *ops, int n_ops, uint64_t *src, uint64_t *wire) {
+    for (int i = 0; i < n_ops; i++) {
+        const ocm_quant_params &p = ops[i];
+        if (p.dtype != OCM_QUANT_BF16 && p.dtype != OCM_QUANT_FP16)
+            OCM_FAIL(-1, "quant op %d: unknown element type %u", i, p.dtype);
+        if (p.elems % kMx8Group != 0 || p.elems >= (1ull << 31))
+            OCM_FAIL(-1, "quant op %d: %llu elements (a multiple of 32 below 2^31 is needed)", i,
+                     (unsigned long long)p.elems);
+        if (p.local_offset % 16 != 0)
+            OCM_FAIL(-1, "quant op %d: local offset %llu is not a multiple of 16", i, (unsigned long long)p.local_offset);
+        if (p.remote_offset % 32 != 0)
+            OCM_FAIL(-1, "quant op %d: remote offset %llu is not a multiple of 32", i,
+                     (unsigned long long)p.remote_offset);
+        const uint64_t lbytes = 2 * p.elems, rbytes = mx8_record_bytes(p.elems);
+        if (p.local_offset > a->local_bytes || lbytes > a->local_bytes - p.local_offset)
+            OCM_FAIL(-1, "quant op %d: local range [%llu,+%llu) exceeds %zu bytes", i,
+                     (unsigned long long)p.local_offset, (unsigned long long)lbytes, a->local_bytes);
+        if (p.remote_offset > a->remote_bytes || rbytes > a->remote_bytes - p.remote_offset)
+            OCM_FAIL(-1, "quant op %d: remote range [%llu,+%llu) exceeds %zu bytes", i,
+                     (unsigned long long)p.remote_offset, (unsigned long long)rbytes, a->remote_bytes);
+        *src += lbytes;
+        *wire += rbytes;
+    }
+    return 0;
+}
+
+// Host local half: op by op, in order; a record is contiguous on the remote side.
+static int quant_host(lib_alloc *a, const struct ocm_quant_params *ops, int n_ops) {
+    State &s = S();
+    if (s.device >= 0) {
+        // the CPU reads and writes the local half: after queued async ops and stream dependencies
+        DeviceGuard guard(s.device);
+        if (wait_alloc(a) != 0) return -1;
+        if (honor_dep(a, nullptr, true) != 0) return -1;
+    }
+    std::vector<uint8_t> rec;
+    for (int i = 0; i < n_ops; i++) {
+        const ocm_quant_params &p = ops[i];
+        if (p.elems == 0) continue;
+        uint16_t *loc = reinterpret_cast<uint16_t *>(static_cast<char *>(a->local) + p.local_offset);
+        const size_t rbytes = mx8_record_bytes(p.elems);
+        rec.resize(rbytes);
+        if (p.op_flag != 0) mx8_encode(loc, p.elems, p.dtype, rec.data());
+        if (xfer(a, p.op_flag != 0, reinterpret_cast<char *>(rec.data()), LOC_HOST, p.remote_offset, rbytes, false) != 0)
+            return -1;
+        if (p.op_flag == 0) mx8_decode(rec.data(), p.elems, p.dtype, loc);
+    }
+    return 0;
+}
+
+static int quant_impl(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags, uint64_t *src,
+                      uint64_t *wire) {
+    State &s = S();
+    std::lock_guard<std::recursive_mutex> lk(s.mu);
+    if (!a || (!ops && n_ops)) OCM_FAIL(-1, "ocm_copy_onesided_quant: NULL argument");
+    if (!s.allocs.count(a)) OCM_FAIL(-1, "ocm_copy_onesided_quant: unknown allocation");
+    if (!a->remote) OCM_FAIL(-1, "converting one-sided copies need a remote pair (kind %d)", (int)a->kind);
+    if (n_ops < 0) OCM_FAIL(-1, "ocm_copy_onesided_quant: n_ops < 0");
+    if (check_quant_ops(a, ops, n_ops, src, wire) != 0) return -1;
+    if (n_ops == 0 || *src == 0) return 0;
+    if (!batch_device_path(a)) {
+        if (a->loc == LOC_DEVICE)
+            OCM_FAIL(-1, "ocm_copy_onesided_quant: a device local half needs every extent reachable by a kernel "
+                         "(no network tier, stripe unit >= 16 bytes)");
+        return quant_host(a, ops, n_ops);
+    }
+    DeviceGuard guard(s.device);
+    XferBatchArgs args;
+    std::vector<XferBatchOp> v((size_t)n_ops, XferBatchOp{});
+    for (int i = 0; i < n_ops; i++) {
+        v[i].lin_off = ops[i].local_offset;
+        v[i].rem_off = ops[i].remote_offset;
+        v[i].len = ops[i].elems;
+        v[i].put = ops[i].op_flag != 0;
+        v[i].pad = ops[i].dtype;
+    }
+    batch_layout_args(a, false, &args);
+    args.tile_shift = kQuantTileShift;
+    args.n_ops = (uint32_t)v.size();
+    args.total_tiles = xfer_quant_plan(v.data(), (uint32_t)v.size());
+    args.grid = xfer_batch_grid(args.total_tiles, args.host_tier != 0);
+    if (v.size() <= (size_t)kXferInlineOps) std::memcpy(args.inline_ops, v.data(), v.size() * sizeof(XferBatchOp));
+    return run_batch(a, args, v, (flags & OCM_BATCH_ASYNC) != 0, true);
+}
+
+extern "C" {
+
+size_t ocm_quant_bytes(uint64_t elems) { return mx8_record_bytes(elems); }
+
+int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags) {
+    TraceRange tr("ocm_quant");
+    const uint64_t t0 = now_ns();
+    uint64_t src = 0, wire = 0;
+    const int rc = quant_impl(a, ops, n_ops, flags, &src, &wire);
+    const uint64_t t1 = now_ns();
+    if (rc == 0) {
+        OpCounters &c = S().ctr;
+        c.n_quant++;
+        c.n_quant_ops += (uint64_t)n_ops;
+        c.bytes_quant_src += src;
+        c.bytes_quant_wire += wire;
+    }
+    trace_op("quant", wire, t0, t1, rc);
+    return rc;
+}
+
+}  // extern "C"

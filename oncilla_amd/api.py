@@ -55,6 +55,18 @@ class OcmParams(ctypes.Structure):
     ]
 
 
+class OcmQuantParams(ctypes.Structure):
+    """struct ocm_quant_params (32 bytes)."""
+
+    _fields_ = [
+        ("local_offset", ctypes.c_uint64),
+        ("remote_offset", ctypes.c_uint64),
+        ("elems", ctypes.c_uint64),
+        ("op_flag", ctypes.c_int32),
+        ("dtype", ctypes.c_uint32),
+    ]
+
+
 class OcmAllocParams(ctypes.Structure):
     """struct ocm_alloc_params (24 bytes)."""
 
@@ -161,6 +173,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_copy_onesided_async": (i32, [vp, ctypes.POINTER(OcmParams)]),
             "ocm_wait": (i32, [vp]),
             "ocm_copy_onesided_batch": (i32, [vp, ctypes.POINTER(OcmParams), i32, i32]),
+            "ocm_quant_bytes": (ctypes.c_size_t, [u64]),
+            "ocm_copy_onesided_quant": (i32, [vp, ctypes.POINTER(OcmQuantParams), i32, i32]),
             "ocm_stream_wait": (i32, [vp, vp]),
             "ocm_plan_create": (vp, []),
             "ocm_plan_add": (i32, [vp, vp, ctypes.POINTER(OcmParams), i32]),
@@ -242,8 +256,11 @@ def last_error() -> str:
 
 COUNTER_KEYS = ["n_put", "n_get", "bytes_put", "bytes_get", "n_alloc", "n_free", "n_copy", "bytes_copy", "ns_put",
                 "ns_get", "ns_alloc", "ns_free", "n_batch", "n_batch_ops", "bytes_batch", "ns_batch",
-                "n_batch_launches", "n_slab_fd", "n_slab_path", "n_link_rpc", "n_link_wake"]
+                "n_batch_launches", "n_slab_fd", "n_slab_path", "n_link_rpc", "n_link_wake",
+                "n_quant", "n_quant_ops", "bytes_quant_src", "bytes_quant_wire"]
 OCM_BATCH_ASYNC = 1
+OCM_QUANT_BF16 = 1
+OCM_QUANT_FP16 = 2
 
 
 class Plan:
@@ -316,6 +333,40 @@ def batch_ops(ops) -> BatchOps:
     for i, (flag, loff, roff, n) in enumerate(ops):
         arr[i] = OcmParams(loff, roff, 0, 0, n, flag)
     return BatchOps(arr, len(ops))
+
+
+def quant_bytes(elems: int) -> int:
+    """Bytes of the MXFP8 record of `elems` 16-bit elements: elems + elems / 32 (ocm_quant_bytes)."""
+    return int(load().ocm_quant_bytes(int(elems)))
+
+
+def quant_dtype(dtype) -> int:
+    """enum ocm_quant_dtype of a torch dtype, of "bf16" / "fp16", or of the enum value itself."""
+    if isinstance(dtype, int):
+        return dtype
+    name = str(dtype).replace("torch.", "")
+    try:
+        return {"bf16": OCM_QUANT_BF16, "bfloat16": OCM_QUANT_BF16, "fp16": OCM_QUANT_FP16, "float16": OCM_QUANT_FP16,
+                "half": OCM_QUANT_FP16}[name]
+    except KeyError:
+        raise ValueError(f"converting ops take bfloat16 or float16 elements, not {dtype}") from None
+
+
+def quant_ops(ops, dtype) -> BatchOps:
+    """Descriptor list for Allocation.quant_batch from an (n, 4) integer array (or rows)
+    [op_flag, local_offset, remote_offset, elems], built once (no per-op Python objects)."""
+    import numpy as np
+
+    a = np.asarray(ops, dtype=np.int64).reshape(-1, 4)
+    n = int(a.shape[0])
+    rec = np.zeros(max(1, n), dtype=np.dtype([("lo", "<u8"), ("ro", "<u8"), ("el", "<u8"), ("flag", "<i4"), ("dt", "<u4")]))
+    if n:
+        rec["lo"][:n], rec["ro"][:n], rec["el"][:n], rec["flag"][:n] = a[:, 1], a[:, 2], a[:, 3], a[:, 0]
+        rec["dt"][:n] = quant_dtype(dtype)
+    b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmQuantParams)), n)
+    b.keep = rec
+    b.quant = True
+    return b
 
 
 def set_tuning(variant: int = 0, blocks: int = 0, nontemporal: bool = True) -> None:
@@ -713,6 +764,19 @@ class Allocation:
         arr = ops if isinstance(ops, BatchOps) else batch_ops(ops)
         if self._c.lib.ocm_copy_onesided_batch(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_batch: " + last_error())
+
+    def quant_batch(self, ops, dtype=None, async_: bool = False) -> None:
+        """Converting one-sided ops in one launch (ocm_copy_onesided_quant): 16-bit elements of
+        `dtype` (torch.bfloat16 / torch.float16) in the local half, MXFP8 records in the remote half.
+
+        ops: an (n, 4) integer array [op_flag, local_offset, remote_offset, elems] with op_flag
+        1 = put (encode), 0 = get (decode); or a prepared :func:`quant_ops` list (dtype then unused).
+        """
+        arr = ops if isinstance(ops, BatchOps) else quant_ops(ops, dtype)
+        if not getattr(arr, "quant", False):
+            raise TypeError("quant_batch takes a quant_ops list, not a batch_ops one")
+        if self._c.lib.ocm_copy_onesided_quant(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
+            raise OcmError("ocm_copy_onesided_quant: " + last_error())
 
     def adam(self, p, g, m_off: int, v_off: int, hp, stream=None, w_off: Optional[int] = None) -> None:
         """Fused Adam on GPU tensors p/g (contiguous) with exp_avg / exp_avg_sq at byte offsets

@@ -9,6 +9,11 @@ other MI355X (xGMI), the pinned host tier, or another node. A whole swap list
 becomes ONE batched one-sided launch (ocm_copy_onesided_batch), with runs of
 consecutive blocks coalesced into single ops.
 
+With ``compress="mxfp8"`` the pool holds MXFP8 records (e4m3fn codes and one
+power-of-two scale byte per 32 elements, ``oncilla_amd.ops.mx8_encode_reference``):
+a block takes 33/64 of its bytes in the pool and on the link, converted as it is
+copied (ocm_copy_onesided_quant), and comes back rounded to that format.
+
 Streams: swap_out waits for work already queued on torch's current stream (the
 kernels that wrote the cache). After an async swap_in, that stream waits for the
 copies, so later attention kernels see the blocks without a host sync.
@@ -46,23 +51,51 @@ class PagedKVOffload:
 
     def __init__(self, client: api.Client, num_gpu_blocks: int, num_pool_blocks: int, block_shape: Sequence[int],
                  dtype=None, kind: int = api.OCM_REMOTE_GPU, flags: int = api.OCM_ALLOC_STRIPE, stripe_unit: int = 0,
-                 remote_rank: int = -1):
+                 remote_rank: int = -1, compress=None):
         import torch
 
         self.dtype = dtype or torch.float16
         self.block_shape = tuple(block_shape)
         elem = torch.empty((), dtype=self.dtype).element_size()
-        self.block_bytes = int(math.prod(self.block_shape)) * elem
+        self.block_elems = int(math.prod(self.block_shape))
+        self.block_bytes = self.block_elems * elem
         self.num_gpu_blocks = num_gpu_blocks
         self.num_pool_blocks = num_pool_blocks
+        self.compress = compress
+        # bytes between pool blocks: the block itself, or its MXFP8 record rounded up to 32
+        self.pool_block_bytes = self.block_bytes
+        if compress is not None:
+            if compress != "mxfp8":
+                raise ValueError(f"unknown compression {compress!r} (None or 'mxfp8')")
+            if self.dtype not in (torch.float16, torch.bfloat16):
+                raise ValueError("compress='mxfp8' needs float16 or bfloat16 blocks")
+            if self.block_elems % 32 or self.block_bytes % 16:
+                raise ValueError("compress='mxfp8' needs a block element count that is a multiple of 32")
+            self.pool_block_bytes = (api.quant_bytes(self.block_elems) + 31) // 32 * 32
         self.alloc = client.alloc(kind, local_bytes=num_gpu_blocks * self.block_bytes,
-                                  remote_bytes=num_pool_blocks * self.block_bytes, remote_rank=remote_rank,
+                                  remote_bytes=num_pool_blocks * self.pool_block_bytes, remote_rank=remote_rank,
                                   flags=flags, stripe_unit=stripe_unit)
         # The cache the model reads and writes: a zero-copy view of the local half.
         self.gpu_cache = self.alloc.local_tensor(self.dtype)[: num_gpu_blocks * self.block_bytes // elem].view(
             num_gpu_blocks, *self.block_shape)
 
+    def _quant_ops(self, pairs, put: bool) -> api.BatchOps:
+        # One op per block, never a coalesced run: a run's record would hold all its codes and
+        # then all its scales, which a later read of one block could not find.
+        a = np.asarray(pairs if isinstance(pairs, np.ndarray) else list(pairs), dtype=np.int64).reshape(-1, 2)
+        g, p = (a[:, 0], a[:, 1]) if put else (a[:, 1], a[:, 0])  # (gpu block, pool block)
+        if len(a) and ((g < 0).any() or (g >= self.num_gpu_blocks).any() or (p < 0).any()
+                       or (p >= self.num_pool_blocks).any()):
+            raise IndexError("block out of range")
+        ops = np.stack([np.full_like(g, 1 if put else 0), g * self.block_bytes, p * self.pool_block_bytes,
+                        np.full_like(g, self.block_elems)], axis=1)
+        if len(a) and len(np.unique(a[:, 1])) != len(a):
+            raise ValueError("compressed swaps take one op per block: a destination block is named twice")
+        return api.quant_ops(ops, self.dtype)
+
     def _ops(self, pairs, put: bool) -> api.BatchOps:
+        if self.compress:
+            return self._quant_ops(pairs, put)
         runs = coalesce_array(pairs if isinstance(pairs, np.ndarray) else list(pairs))
         g, p = (runs[:, 0], runs[:, 1]) if put else (runs[:, 1], runs[:, 0])  # (gpu block, pool block)
         n = runs[:, 2]
@@ -73,11 +106,17 @@ class PagedKVOffload:
         ops = np.stack([np.full_like(n, 1 if put else 0), g * bb, p * bb, n * bb], axis=1)
         return api.batch_ops(ops)
 
+    def _run(self, ops: api.BatchOps, async_: bool) -> None:
+        if self.compress:
+            self.alloc.quant_batch(ops, async_=async_)
+        else:
+            self.alloc.batch(ops, async_=async_)
+
     def swap_out(self, gpu_to_pool: Iterable[tuple[int, int]], async_: bool = True) -> int:
         """Copy GPU blocks to pool blocks. Returns the number of batched ops issued."""
         ops = self._ops(gpu_to_pool, put=True)
         self.alloc.stream_wait()  # after the kernels that produced the blocks
-        self.alloc.batch(ops, async_=async_)
+        self._run(ops, async_)
         if async_:
             self.alloc.stream_signal()  # and before anything that overwrites them
         return ops.n
@@ -86,7 +125,7 @@ class PagedKVOffload:
         """Copy pool blocks into GPU blocks; torch's current stream waits for them."""
         ops = self._ops(pool_to_gpu, put=False)
         self.alloc.stream_wait()  # do not overwrite blocks still being read
-        self.alloc.batch(ops, async_=async_)
+        self._run(ops, async_)
         if async_:
             self.alloc.stream_signal()
         return ops.n

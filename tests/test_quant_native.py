@@ -1,0 +1,43 @@
+"""The MXFP8 host codec (csrc/include/ocm/mx8.h) on fixed vectors: the stand-alone
+program csrc/tools/ocm_quant_tests.cpp, as built and as built with ASan + UBSan (host
+code only, run directly: nothing is preloaded and nothing is loaded into Python)."""
+import pytest
+
+from oncilla_amd.utils.paths import BUILD_DIR
+
+PARTS = ("edge_groups", "amax_sweep", "fp16_convert", "e4m3_codes", "record_layout")
+
+
+@pytest.mark.parametrize("binary", ["ocm_quant_tests", "ocm_quant_tests_asan"])
+def test_host_codec_vectors(native, tool, binary):
+    rc, out = tool([f"{native}/{binary}"])
+    assert rc == 0, out
+    for name in PARTS:
+        assert f"PASS {name}" in out, out
+    assert "runtime error" not in out and "AddressSanitizer" not in out, out
+
+
+def test_quant_kernel_uses_no_scratch():
+    # as tests/test_native_unit.py does for the other kernels: the extent table is indexed
+    # per lane here, which must stay a load from the kernel arguments, never a scratch copy
+    import os
+    import re
+    import subprocess
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{repo}/csrc/include",
+                        "-c", f"{repo}/csrc/src/kernels/xfer_quant.hip", "-o", os.devnull,
+                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
+    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
+    assert len(names) >= 2 and len(scratch) == len(names)
+    assert all(s == 0 for s in scratch), dict(zip(names, scratch))
+    assert all(s == 0 for s in spills), dict(zip(names, spills))
+
+
+def test_registered_with_ctest(native, tool):
+    rc, out = tool(["ctest", "--test-dir", BUILD_DIR, "-N"])
+    assert rc == 0, out
+    assert "ocm_quant_tests" in out and "ocm_quant_tests_asan" in out
