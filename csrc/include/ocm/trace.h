@@ -21,6 +21,8 @@ struct OpCounters {
     uint64_t n_slab_path = 0;       // ... through the /proc/<pid>/fd path fallback
     uint64_t n_link_rpc = 0;        // RPCs posted on the shared-memory link (ocm/shmlink.h)
     uint64_t n_link_wake = 0;       // ... of which had to wake the daemon over the socket
+    // strided ops (ocm_copy_onesided_strided): calls, ops, bytes moved (rows * row_bytes)
+    uint64_t n_strided = 0, n_strided_ops = 0, bytes_strided = 0;
 };
 
 bool trace_enabled();  // OCM_TRACE=0 disables the roctx ranges

@@ -143,6 +143,11 @@ hipError_t xfer_batch_launch(const XferBatchArgs &a, const XferTuning &t, hipStr
 hipError_t xfer_batch_graph_node(hipGraph_t graph, hipGraphNode_t dep, const XferBatchArgs &a, const XferTuning &t,
                                  hipGraphNode_t *node);
 
+// Strided lists (ocm/strided.h: the descriptors, the tile geometry and the host plan):
+// one launch; a.grid from xfer_batch_grid, a.wave_op from xfer_strided_wave_ops.
+struct XferStridedArgs;
+hipError_t xfer_strided_launch(const XferStridedArgs &a, const XferTuning &t, hipStream_t stream);
+
 // ---- persistent copy service (low-latency blocking one-sided ops) ----
 // A resident gang of `blocks` workgroups. Workgroup 0 polls one 128-byte
 // request record {args, gang, sum, seq} in host-pinned memory (ServiceReq),

@@ -172,6 +172,27 @@ struct ocm_quant_params {
 /* Bytes of the record of `elems` elements: elems + elems / 32. */
 size_t ocm_quant_bytes(uint64_t elems);
 int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags);
+/* Strided one-sided copies (2-D put / get): row r of an op moves row_bytes bytes between
+ * local[local_offset + r * local_stride] and remote[remote_offset + r * remote_stride],
+ * r = 0 .. rows - 1, in the direction of ocm_copy_onesided (op_flag 1 = put). Ops of one
+ * call and rows of one op run concurrently, puts and gets mixed, as ONE gfx950 launch
+ * when the local half is device memory: overlapping destinations have no defined order.
+ * No alignment is asked of offsets, strides or row_bytes. Per op: reserved == 0,
+ * rows < 2^32, with rows > 1 both strides >= row_bytes, and the last row's end inside
+ * its half on both sides; an op with rows == 0 or row_bytes == 0 does nothing. flags and
+ * ordering as for ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait,
+ * ocm_stream_wait/signal). Transfer plans (ocm_plan_add) take ocm_params only. */
+struct ocm_strided_params {
+    uint64_t local_offset;   /* first byte of row 0 in the local half  */
+    uint64_t remote_offset;  /* first byte of row 0 in the remote half */
+    uint64_t row_bytes;      /* bytes per row (any value, 0 = empty op) */
+    uint64_t rows;           /* number of rows, < 2^32 */
+    uint64_t local_stride;   /* bytes from one row's start to the next, local half  */
+    uint64_t remote_stride;  /* same, remote half */
+    int32_t  op_flag;        /* 1 = put, 0 = get */
+    uint32_t reserved;       /* must be 0 */
+};
+int ocm_copy_onesided_strided(ocm_alloc_t a, const struct ocm_strided_params *ops, int n_ops, int flags);
 /* Stream interop (hipStream_t passed as void*, NULL = legacy default stream):
  * ocm_stream_wait:   a's next one-sided op starts after the work already queued on `stream`
  *                    (e.g. torch kernels that wrote the local half).

@@ -68,20 +68,23 @@ bool batch_device_path(const lib_alloc *a) {
            (a->ext.size() == 1 || log2_exact(a->stripe_unit) >= 4);
 }
 
-// Upload (large lists), launch and complete one batch on `a`. `args` from plan_batch_args,
-// or a converting list's (quant.cpp; `quant`: the launch is xfer_quant_launch).
-int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, bool quant) {
+// Upload (large lists), launch and complete one descriptor list on `a`: the staging
+// buffer, its batch_up event and the completion every list kind shares. `list.large`:
+// the descriptors and the per-wave starting ops (4 per workgroup of `grid`) go to device
+// memory in one upload, and `launch` gets their addresses there (else nullptr twice).
+int run_list(lib_alloc *a, const BatchList &list, bool async) {
     State &s = S();
     DeviceGuard guard(s.device);
     if (!async && wait_alloc(a) != 0) return -1;
     hipStream_t st = async ? lane_stream(a) : s.stream;
     if (honor_dep(a, st, false) != 0) return -1;
     hipError_t err = hipSuccess;
-    const size_t n_ops = v.size();
-    if (n_ops > (size_t)kXferInlineOps) {
+    const void *dev_desc = nullptr;
+    const uint32_t *dev_wave = nullptr;
+    if (list.large) {
         // descriptors, then the per-wave starting ops, in one upload
-        const size_t dbytes = v.size() * sizeof(XferBatchOp);
-        const size_t need = dbytes + (size_t)args.grid * 4 * sizeof(uint32_t);
+        const size_t dbytes = list.desc_bytes;
+        const size_t need = dbytes + (size_t)list.grid * 4 * sizeof(uint32_t);
         if (a->batch_up && hipEventSynchronize(a->batch_up) != hipSuccess)  // staging free again
             OCM_FAIL(-1, "batch staging wait failed");
         if (a->batch_cap < need) {
@@ -100,19 +103,19 @@ int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bo
             a->batch_cap = cap;
         }
         char *up = static_cast<char *>(a->batch_host);
-        std::memcpy(up, v.data(), dbytes);
-        xfer_batch_wave_ops(v.data(), (uint32_t)n_ops, args.total_tiles, args.grid, reinterpret_cast<uint32_t *>(up + dbytes));
+        std::memcpy(up, list.desc, dbytes);
+        list.wave_ops(list.ctx, reinterpret_cast<uint32_t *>(up + dbytes));
         // Pinned source: a real async DMA; batch_up tells the next batch when `up` is free.
         err = hipMemcpyAsync(a->batch_dev, up, need, hipMemcpyHostToDevice, st);
         if (err == hipSuccess) err = hipEventRecord(a->batch_up, st);
         if (err != hipSuccess) OCM_FAIL(-1, "batch descriptor upload: %s", hipGetErrorString(err));
-        args.ops = static_cast<const XferBatchOp *>(a->batch_dev);
-        args.wave_op = reinterpret_cast<const uint32_t *>(static_cast<char *>(a->batch_dev) + dbytes);
+        dev_desc = a->batch_dev;
+        dev_wave = reinterpret_cast<const uint32_t *>(static_cast<char *>(a->batch_dev) + dbytes);
     }
     before_launch();
-    err = quant ? xfer_quant_launch(args, s.tuning, st) : xfer_batch_launch(args, s.tuning, st);
+    err = list.launch(list.ctx, dev_desc, dev_wave, st);
     if (err != hipSuccess) OCM_FAIL(-1, "batch launch failed: %s", hipGetErrorString(err));
-    if (!quant) s.ctr.n_batch_launches++;
+    if (list.count_launch) s.ctr.n_batch_launches++;
     if (async) {
         if (st != s.stream && a->ev) {
             err = hipEventRecord(a->ev, st);
@@ -122,6 +125,36 @@ int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bo
         }
     }
     return sync_stream();
+}
+
+// One batch on `a`. `args` from plan_batch_args, or a converting list's (quant.cpp;
+// `quant`: the launch is xfer_quant_launch).
+int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, bool quant) {
+    struct Ctx {
+        XferBatchArgs &args;
+        std::vector<XferBatchOp> &v;
+        bool quant;
+    } ctx{args, v, quant};
+    BatchList list;
+    list.desc = v.data();
+    list.desc_bytes = v.size() * sizeof(XferBatchOp);
+    list.large = v.size() > (size_t)kXferInlineOps;
+    list.grid = args.grid;
+    list.count_launch = !quant;
+    list.ctx = &ctx;
+    list.wave_ops = [](void *p, uint32_t *out) {
+        Ctx &c = *static_cast<Ctx *>(p);
+        xfer_batch_wave_ops(c.v.data(), (uint32_t)c.v.size(), c.args.total_tiles, c.args.grid, out);
+    };
+    list.launch = [](void *p, const void *dev_desc, const uint32_t *dev_wave, hipStream_t st) {
+        Ctx &c = *static_cast<Ctx *>(p);
+        if (dev_desc) {
+            c.args.ops = static_cast<const XferBatchOp *>(dev_desc);
+            c.args.wave_op = dev_wave;
+        }
+        return c.quant ? xfer_quant_launch(c.args, S().tuning, st) : xfer_batch_launch(c.args, S().tuning, st);
+    };
+    return run_list(a, list, async);
 }
 
 // Remote -> remote copies: every op's linear side is an absolute device address

@@ -5,6 +5,7 @@
 // net.cpp      network-tier client (owners on other nodes)
 // batch.cpp    batched one-sided ops, stream interop, transfer plans (hipGraph)
 // quant.cpp    converting one-sided ops (ocm_copy_onesided_quant: MXFP8 records)
+// strided.cpp  strided one-sided ops (ocm_copy_onesided_strided: rows, one stride per side)
 // libocm.cpp   the C ABI (oncillamem.h)
 #pragma once
 #include <fcntl.h>
@@ -549,6 +550,18 @@ void push_release();
 char *extent_view(const Extent &e, int dev);
 
 // ---- batches (batch.cpp)
+// What run_list needs of a descriptor list, whatever its kind (batch, converting, strided).
+struct BatchList {
+    const void *desc = nullptr;  // the planned descriptors (host)
+    size_t desc_bytes = 0;
+    bool large = false;          // more descriptors than travel in the kernel arguments: upload them
+    uint32_t grid = 0;           // workgroups; the wave table has 4 entries for each
+    bool count_launch = false;   // counts in n_batch_launches
+    void *ctx = nullptr;         // the caller's launch arguments, handed to both functions
+    void (*wave_ops)(void *ctx, uint32_t *out) = nullptr;  // fills the wave table (large lists)
+    hipError_t (*launch)(void *ctx, const void *dev_desc, const uint32_t *dev_wave, hipStream_t st) = nullptr;
+};
+int run_list(lib_alloc *a, const BatchList &list, bool async);
 int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, bool quant = false);
 bool batch_device_path(const lib_alloc *a);
 void batch_layout_args(lib_alloc *a, bool abs_lin, XferBatchArgs *args);

@@ -814,14 +814,15 @@ const char *ocm_last_error(void) { return last_error(); }
 
 // ---------------- internal hooks for tests and benchmarks (not part of the ABI) ----------------
 
-// Per-process operation counters (see ocm/trace.h): 25 x uint64.
-void ocm_x_counters(uint64_t out[25]) {
+// Per-process operation counters (see ocm/trace.h): 28 x uint64.
+void ocm_x_counters(uint64_t out[28]) {
     const OpCounters &c = S().ctr;
-    const uint64_t v[25] = {c.n_put,  c.n_get,    c.bytes_put, c.bytes_get,   c.n_alloc,     c.n_free,
+    const uint64_t v[28] = {c.n_put,  c.n_get,    c.bytes_put, c.bytes_get,   c.n_alloc,     c.n_free,
                             c.n_copy, c.bytes_copy, c.ns_put,  c.ns_get,      c.ns_alloc,    c.ns_free,
                             c.n_batch, c.n_batch_ops, c.bytes_batch, c.ns_batch, c.n_batch_launches,
                             c.n_slab_fd, c.n_slab_path, c.n_link_rpc, c.n_link_wake,
-                            c.n_quant, c.n_quant_ops, c.bytes_quant_src, c.bytes_quant_wire};
+                            c.n_quant, c.n_quant_ops, c.bytes_quant_src, c.bytes_quant_wire,
+                            c.n_strided, c.n_strided_ops, c.bytes_strided};
     std::memcpy(out, v, sizeof(v));
 }
 

@@ -2,10 +2,12 @@
 pool in other GPUs' HBM (or the pinned host tier on a single-daemon node) and
 back, each swap list being one batched launch ordered against torch's stream.
 
-    python examples/kv_offload.py [--daemons 4] [--compress]
+    python examples/kv_offload.py [--daemons 4] [--compress | --layers N]
 
 --compress keeps the pool as MXFP8 records (33/64 of the bytes in the pool and on the
 link); blocks then come back rounded to that format.
+--layers N keeps one cache per layer, [N, blocks, ...], as serving engines do: a block is
+N pieces a cache apart, and each swapped block is one strided op (rows = N).
 """
 import argparse
 import os
@@ -20,11 +22,30 @@ from oncilla_amd.models import PagedKVOffload  # noqa: E402
 from oncilla_amd.parallel import Mesh  # noqa: E402
 
 
+def layered(args):
+    with Mesh(args.daemons, gpus=[0] * args.daemons, policy="stripe") as mesh:
+        with api.Client(daemon_rank=0, gpu=0, ns=mesh.ns) as c:
+            # per layer: 256 GPU blocks of (K/V, 16 tokens, 8 heads, 8 dims) fp16 = 4 KiB; pool of 2048 blocks
+            kv = PagedKVOffload(c, 256, 2048, (2, 16, 8, 8), dtype=torch.float16, layers=args.layers)
+            kv.gpu_cache.normal_()
+            before = kv.gpu_cache[:, :64].clone()
+            n = kv.swap_out([(g, 1000 + g) for g in range(64)])  # 64 blocks out: one strided op each, one launch
+            kv.gpu_cache[:, :64].zero_()
+            kv.swap_in([(1000 + g, g) for g in range(64)])
+            assert torch.equal(kv.gpu_cache[:, :64], before)      # every layer of every block
+            print(f"64 KV blocks x {args.layers} layers swapped out and back as {n} strided ops; "
+                  f"pool block: {kv.pool_block_bytes} bytes, layer-major")
+            kv.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--daemons", type=int, default=4)
     ap.add_argument("--compress", action="store_true", help="keep the pool MXFP8-compressed (compress='mxfp8')")
+    ap.add_argument("--layers", type=int, default=0, help="one cache per layer: gpu_cache is [N, blocks, ...] (layers=N)")
     args = ap.parse_args()
+    if args.layers:
+        return layered(args)
     with Mesh(args.daemons, gpus=[0] * args.daemons, policy="stripe") as mesh:
         with api.Client(daemon_rank=0, gpu=0, ns=mesh.ns) as c:
             # 256 GPU blocks of (K/V, 16 tokens, 8 heads, 128 dims) fp16 = 64 KiB; pool of 2048 blocks

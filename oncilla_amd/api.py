@@ -67,6 +67,21 @@ class OcmQuantParams(ctypes.Structure):
     ]
 
 
+class OcmStridedParams(ctypes.Structure):
+    """struct ocm_strided_params (56 bytes)."""
+
+    _fields_ = [
+        ("local_offset", ctypes.c_uint64),
+        ("remote_offset", ctypes.c_uint64),
+        ("row_bytes", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("local_stride", ctypes.c_uint64),
+        ("remote_stride", ctypes.c_uint64),
+        ("op_flag", ctypes.c_int32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 class OcmAllocParams(ctypes.Structure):
     """struct ocm_alloc_params (24 bytes)."""
 
@@ -175,6 +190,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_copy_onesided_batch": (i32, [vp, ctypes.POINTER(OcmParams), i32, i32]),
             "ocm_quant_bytes": (ctypes.c_size_t, [u64]),
             "ocm_copy_onesided_quant": (i32, [vp, ctypes.POINTER(OcmQuantParams), i32, i32]),
+            "ocm_copy_onesided_strided": (i32, [vp, ctypes.POINTER(OcmStridedParams), i32, i32]),
             "ocm_stream_wait": (i32, [vp, vp]),
             "ocm_plan_create": (vp, []),
             "ocm_plan_add": (i32, [vp, vp, ctypes.POINTER(OcmParams), i32]),
@@ -257,7 +273,8 @@ def last_error() -> str:
 COUNTER_KEYS = ["n_put", "n_get", "bytes_put", "bytes_get", "n_alloc", "n_free", "n_copy", "bytes_copy", "ns_put",
                 "ns_get", "ns_alloc", "ns_free", "n_batch", "n_batch_ops", "bytes_batch", "ns_batch",
                 "n_batch_launches", "n_slab_fd", "n_slab_path", "n_link_rpc", "n_link_wake",
-                "n_quant", "n_quant_ops", "bytes_quant_src", "bytes_quant_wire"]
+                "n_quant", "n_quant_ops", "bytes_quant_src", "bytes_quant_wire",
+                "n_strided", "n_strided_ops", "bytes_strided"]
 OCM_BATCH_ASYNC = 1
 OCM_QUANT_BF16 = 1
 OCM_QUANT_FP16 = 2
@@ -366,6 +383,26 @@ def quant_ops(ops, dtype) -> BatchOps:
     b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmQuantParams)), n)
     b.keep = rec
     b.quant = True
+    return b
+
+
+def strided_ops(ops) -> BatchOps:
+    """Descriptor list for Allocation.strided_batch from an (n, 7) integer array (or rows)
+    [op_flag, local_offset, remote_offset, row_bytes, rows, local_stride, remote_stride],
+    built once (no per-op Python objects)."""
+    import numpy as np
+
+    a = np.asarray(ops)
+    a = (a if a.dtype == np.uint64 else a.astype(np.int64)).reshape(-1, 7)
+    n = int(a.shape[0])
+    rec = np.zeros(max(1, n), dtype=np.dtype([("lo", "<u8"), ("ro", "<u8"), ("rb", "<u8"), ("rows", "<u8"), ("ls", "<u8"),
+                                              ("rs", "<u8"), ("flag", "<i4"), ("rsv", "<u4")]))
+    if n:
+        for col, name in enumerate(("flag", "lo", "ro", "rb", "rows", "ls", "rs")):
+            rec[name][:n] = a[:, col]
+    b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmStridedParams)), n)
+    b.keep = rec
+    b.strided = True
     return b
 
 
@@ -777,6 +814,21 @@ class Allocation:
             raise TypeError("quant_batch takes a quant_ops list, not a batch_ops one")
         if self._c.lib.ocm_copy_onesided_quant(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_quant: " + last_error())
+
+    def strided_batch(self, ops, async_: bool = False) -> None:
+        """Strided one-sided ops in one launch (ocm_copy_onesided_strided): row r of an op moves
+        row_bytes bytes between local[local_offset + r * local_stride] and
+        remote[remote_offset + r * remote_stride].
+
+        ops: an (n, 7) integer array [op_flag, local_offset, remote_offset, row_bytes, rows,
+        local_stride, remote_stride] with op_flag 1 = put, 0 = get; or a prepared
+        :func:`strided_ops` list.
+        """
+        arr = ops if isinstance(ops, BatchOps) else strided_ops(ops)
+        if not getattr(arr, "strided", False):
+            raise TypeError("strided_batch takes a strided_ops list, not a batch_ops or quant_ops one")
+        if self._c.lib.ocm_copy_onesided_strided(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
+            raise OcmError("ocm_copy_onesided_strided: " + last_error())
 
     def adam(self, p, g, m_off: int, v_off: int, hp, stream=None, w_off: Optional[int] = None) -> None:
         """Fused Adam on GPU tensors p/g (contiguous) with exp_avg / exp_avg_sq at byte offsets

@@ -14,6 +14,12 @@ power-of-two scale byte per 32 elements, ``oncilla_amd.ops.mx8_encode_reference`
 a block takes 33/64 of its bytes in the pool and on the link, converted as it is
 copied (ocm_copy_onesided_quant), and comes back rounded to that format.
 
+With ``layers=L`` the GPU cache has the layout serving engines use, one cache per
+layer: ``[L, num_gpu_blocks, *block_shape]``. A logical block is then L pieces of
+block_bytes, num_gpu_blocks * block_bytes apart; in the pool it is L * block_bytes
+contiguous bytes, layer-major. Each swapped block is one strided op
+(ocm_copy_onesided_strided, rows = L) and the whole list still one launch.
+
 Streams: swap_out waits for work already queued on torch's current stream (the
 kernels that wrote the cache). After an async swap_in, that stream waits for the
 copies, so later attention kernels see the blocks without a host sync.
@@ -51,7 +57,7 @@ class PagedKVOffload:
 
     def __init__(self, client: api.Client, num_gpu_blocks: int, num_pool_blocks: int, block_shape: Sequence[int],
                  dtype=None, kind: int = api.OCM_REMOTE_GPU, flags: int = api.OCM_ALLOC_STRIPE, stripe_unit: int = 0,
-                 remote_rank: int = -1, compress=None):
+                 remote_rank: int = -1, compress=None, layers: int = 0):
         import torch
 
         self.dtype = dtype or torch.float16
@@ -62,6 +68,11 @@ class PagedKVOffload:
         self.num_gpu_blocks = num_gpu_blocks
         self.num_pool_blocks = num_pool_blocks
         self.compress = compress
+        self.layers = int(layers)
+        if self.layers < 0:
+            raise ValueError("layers must be 0 (one cache of whole blocks) or the number of per-layer caches")
+        if self.layers and compress is not None:
+            raise ValueError("layers > 0 cannot be combined with compress: converting ops are not strided")
         # bytes between pool blocks: the block itself, or its MXFP8 record rounded up to 32
         self.pool_block_bytes = self.block_bytes
         if compress is not None:
@@ -72,12 +83,15 @@ class PagedKVOffload:
             if self.block_elems % 32 or self.block_bytes % 16:
                 raise ValueError("compress='mxfp8' needs a block element count that is a multiple of 32")
             self.pool_block_bytes = (api.quant_bytes(self.block_elems) + 31) // 32 * 32
-        self.alloc = client.alloc(kind, local_bytes=num_gpu_blocks * self.block_bytes,
+        if self.layers:
+            self.pool_block_bytes = self.layers * self.block_bytes  # a block's layers side by side
+        lead = (self.layers, num_gpu_blocks) if self.layers else (num_gpu_blocks,)
+        local_bytes = math.prod(lead) * self.block_bytes
+        self.alloc = client.alloc(kind, local_bytes=local_bytes,
                                   remote_bytes=num_pool_blocks * self.pool_block_bytes, remote_rank=remote_rank,
                                   flags=flags, stripe_unit=stripe_unit)
         # The cache the model reads and writes: a zero-copy view of the local half.
-        self.gpu_cache = self.alloc.local_tensor(self.dtype)[: num_gpu_blocks * self.block_bytes // elem].view(
-            num_gpu_blocks, *self.block_shape)
+        self.gpu_cache = self.alloc.local_tensor(self.dtype)[: local_bytes // elem].view(*lead, *self.block_shape)
 
     def _quant_ops(self, pairs, put: bool) -> api.BatchOps:
         # One op per block, never a coalesced run: a run's record would hold all its codes and
@@ -93,9 +107,26 @@ class PagedKVOffload:
             raise ValueError("compressed swaps take one op per block: a destination block is named twice")
         return api.quant_ops(ops, self.dtype)
 
+    def _strided_ops(self, pairs, put: bool) -> api.BatchOps:
+        # One op per block: rows = layers, a cache apart on the GPU, side by side in the pool.
+        a = np.asarray(pairs if isinstance(pairs, np.ndarray) else list(pairs), dtype=np.int64).reshape(-1, 2)
+        g, p = (a[:, 0], a[:, 1]) if put else (a[:, 1], a[:, 0])  # (gpu block, pool block)
+        if len(a) and ((g < 0).any() or (g >= self.num_gpu_blocks).any() or (p < 0).any()
+                       or (p >= self.num_pool_blocks).any()):
+            raise IndexError("block out of range")
+        if len(a) and len(np.unique(a[:, 1])) != len(a):
+            raise ValueError("layered swaps take one op per block: a destination block is named twice")
+        bb = self.block_bytes
+        ops = np.stack([np.full_like(g, 1 if put else 0), g * bb, p * self.pool_block_bytes, np.full_like(g, bb),
+                        np.full_like(g, self.layers), np.full_like(g, self.num_gpu_blocks * bb), np.full_like(g, bb)],
+                       axis=1)
+        return api.strided_ops(ops)
+
     def _ops(self, pairs, put: bool) -> api.BatchOps:
         if self.compress:
             return self._quant_ops(pairs, put)
+        if self.layers:
+            return self._strided_ops(pairs, put)
         runs = coalesce_array(pairs if isinstance(pairs, np.ndarray) else list(pairs))
         g, p = (runs[:, 0], runs[:, 1]) if put else (runs[:, 1], runs[:, 0])  # (gpu block, pool block)
         n = runs[:, 2]
@@ -109,6 +140,8 @@ class PagedKVOffload:
     def _run(self, ops: api.BatchOps, async_: bool) -> None:
         if self.compress:
             self.alloc.quant_batch(ops, async_=async_)
+        elif self.layers:
+            self.alloc.strided_batch(ops, async_=async_)
         else:
             self.alloc.batch(ops, async_=async_)
 
