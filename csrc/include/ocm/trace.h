@@ -23,6 +23,8 @@ struct OpCounters {
     uint64_t n_link_wake = 0;       // ... of which had to wake the daemon over the socket
     // strided ops (ocm_copy_onesided_strided): calls, ops, bytes moved (rows * row_bytes)
     uint64_t n_strided = 0, n_strided_ops = 0, bytes_strided = 0;
+    // accumulates (ocm_copy_onesided_accumulate): calls, ops, accumulator bytes updated (4 * elems)
+    uint64_t n_acc = 0, n_acc_ops = 0, bytes_acc = 0;
 };
 
 bool trace_enabled();  // OCM_TRACE=0 disables the roctx ranges

@@ -148,6 +148,11 @@ hipError_t xfer_batch_graph_node(hipGraph_t graph, hipGraphNode_t dep, const Xfe
 struct XferStridedArgs;
 hipError_t xfer_strided_launch(const XferStridedArgs &a, const XferTuning &t, hipStream_t stream);
 
+// Accumulate lists (ocm/acc.h: the element rule, the tile count and the descriptor
+// packing): one launch; a.grid from xfer_batch_grid, a.wave_op from xfer_batch_wave_ops.
+// Stores are nontemporal (t.nontemporal), plain into a pool wholly in the pinned host tier.
+hipError_t xfer_acc_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream);
+
 // ---- persistent copy service (low-latency blocking one-sided ops) ----
 // A resident gang of `blocks` workgroups. Workgroup 0 polls one 128-byte
 // request record {args, gang, sum, seq} in host-pinned memory (ServiceReq),

@@ -193,6 +193,30 @@ struct ocm_strided_params {
     uint32_t reserved;       /* must be 0 */
 };
 int ocm_copy_onesided_strided(ocm_alloc_t a, const struct ocm_strided_params *ops, int n_ops, int flags);
+/* One-sided accumulate (the counterpart of MPI_Accumulate): the remote half holds fp32
+ * accumulators, the local half elements of `dtype`, and for every element i of every op
+ *     remote_f32[i] = remote_f32[i] + scale * widen(local[i]).
+ * The result is defined bit for bit (ocm/acc.h): two IEEE fp32 operations, each rounded
+ * to nearest even, p = scale * x then r = acc + p, never fused into one; subnormals are
+ * kept; bf16 and fp16 elements widen exactly; a NaN result is some NaN. The local half
+ * is only read. Ops of one call run concurrently, as ONE gfx950 launch when the local
+ * half is device memory; no atomics are used, so overlapping remote ranges within one
+ * call have no defined result. Two calls on one allocation are ordered, as batches are.
+ * Per op: dtype known, scale finite, both offsets multiples of 16, elems % 4 == 0 and
+ * elems < 2^31 (0 = empty op), elems * size(dtype) bytes inside the local half and
+ * 4 * elems inside the remote half. flags and ordering as for ocm_copy_onesided_batch
+ * (OCM_BATCH_ASYNC, ocm_wait, ocm_stream_wait/signal). Out of scope: transfer plans
+ * (ocm_plan_add takes ocm_params only), the copy service, a get-side accumulate
+ * (local += remote) and integer element types. */
+enum ocm_acc_dtype { OCM_ACC_F32 = 1, OCM_ACC_BF16 = 2, OCM_ACC_FP16 = 3 };
+struct ocm_acc_params {      /* 32 bytes */
+    uint64_t local_offset;   /* bytes into the local half, multiple of 16 */
+    uint64_t remote_offset;  /* bytes into the remote half (fp32 accumulators), multiple of 16 */
+    uint64_t elems;          /* multiple of 4, below 2^31; 0 = empty op */
+    uint32_t dtype;          /* enum ocm_acc_dtype: element type of the LOCAL half */
+    float    scale;          /* finite */
+};
+int ocm_copy_onesided_accumulate(ocm_alloc_t a, const struct ocm_acc_params *ops, int n_ops, int flags);
 /* Stream interop (hipStream_t passed as void*, NULL = legacy default stream):
  * ocm_stream_wait:   a's next one-sided op starts after the work already queued on `stream`
  *                    (e.g. torch kernels that wrote the local half).

@@ -127,20 +127,21 @@ int run_list(lib_alloc *a, const BatchList &list, bool async) {
     return sync_stream();
 }
 
-// One batch on `a`. `args` from plan_batch_args, or a converting list's (quant.cpp;
-// `quant`: the launch is xfer_quant_launch).
-int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, bool quant) {
+// One batch on `a`. `args` from plan_batch_args, or those of a converting list (quant.cpp,
+// LIST_QUANT: the launch is xfer_quant_launch) or an accumulate list (acc.cpp, LIST_ACC:
+// xfer_acc_launch), whose descriptors are XferBatchOp records too.
+int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, int kind) {
     struct Ctx {
         XferBatchArgs &args;
         std::vector<XferBatchOp> &v;
-        bool quant;
-    } ctx{args, v, quant};
+        int kind;
+    } ctx{args, v, kind};
     BatchList list;
     list.desc = v.data();
     list.desc_bytes = v.size() * sizeof(XferBatchOp);
     list.large = v.size() > (size_t)kXferInlineOps;
     list.grid = args.grid;
-    list.count_launch = !quant;
+    list.count_launch = kind == LIST_BATCH;
     list.ctx = &ctx;
     list.wave_ops = [](void *p, uint32_t *out) {
         Ctx &c = *static_cast<Ctx *>(p);
@@ -152,7 +153,8 @@ int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bo
             c.args.ops = static_cast<const XferBatchOp *>(dev_desc);
             c.args.wave_op = dev_wave;
         }
-        return c.quant ? xfer_quant_launch(c.args, S().tuning, st) : xfer_batch_launch(c.args, S().tuning, st);
+        if (c.kind == LIST_ACC) return xfer_acc_launch(c.args, S().tuning, st);
+        return c.kind == LIST_QUANT ? xfer_quant_launch(c.args, S().tuning, st) : xfer_batch_launch(c.args, S().tuning, st);
     };
     return run_list(a, list, async);
 }

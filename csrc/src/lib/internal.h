@@ -6,6 +6,7 @@
 // batch.cpp    batched one-sided ops, stream interop, transfer plans (hipGraph)
 // quant.cpp    converting one-sided ops (ocm_copy_onesided_quant: MXFP8 records)
 // strided.cpp  strided one-sided ops (ocm_copy_onesided_strided: rows, one stride per side)
+// acc.cpp      one-sided accumulate (ocm_copy_onesided_accumulate: remote fp32 += scale * local)
 // libocm.cpp   the C ABI (oncillamem.h)
 #pragma once
 #include <fcntl.h>
@@ -562,7 +563,9 @@ struct BatchList {
     hipError_t (*launch)(void *ctx, const void *dev_desc, const uint32_t *dev_wave, hipStream_t st) = nullptr;
 };
 int run_list(lib_alloc *a, const BatchList &list, bool async);
-int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, bool quant = false);
+// Which launch reads a list of XferBatchOp records.
+enum ListKind : int { LIST_BATCH = 0, LIST_QUANT = 1, LIST_ACC = 2 };
+int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, int kind = LIST_BATCH);
 bool batch_device_path(const lib_alloc *a);
 void batch_layout_args(lib_alloc *a, bool abs_lin, XferBatchArgs *args);
 // Copy absolute device ranges (op.lin_off = address) into dst's remote half, one launch.

@@ -826,6 +826,14 @@ void ocm_x_counters(uint64_t out[28]) {
     std::memcpy(out, v, sizeof(v));
 }
 
+// The accumulate counters (ocm_x_counters keeps its 28 entries): calls, ops, accumulator bytes.
+void ocm_x_acc_counters(uint64_t out[3]) {
+    const OpCounters &c = S().ctr;
+    out[0] = c.n_acc;
+    out[1] = c.n_acc_ops;
+    out[2] = c.bytes_acc;
+}
+
 // Fused Adam over optimizer state kept in the remote half of `a` (see
 // ocm/optim.h): p/g are this GPU's parameters and gradients (n floats),
 // exp_avg / exp_avg_sq of element 0 sit at byte offsets m_off / v_off of the

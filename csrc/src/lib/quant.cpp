@@ -92,7 +92,7 @@ static int quant_impl(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_o
     args.total_tiles = xfer_quant_plan(v.data(), (uint32_t)v.size());
     args.grid = xfer_batch_grid(args.total_tiles, args.host_tier != 0);
     if (v.size() <= (size_t)kXferInlineOps) std::memcpy(args.inline_ops, v.data(), v.size() * sizeof(XferBatchOp));
-    return run_batch(a, args, v, (flags & OCM_BATCH_ASYNC) != 0, true);
+    return run_batch(a, args, v, (flags & OCM_BATCH_ASYNC) != 0, LIST_QUANT);
 }
 
 extern "C" {

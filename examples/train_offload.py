@@ -6,7 +6,11 @@ striped over them (on a one-GPU box the daemons share GPU 0), and one fused
 gfx950 kernel per parameter updates them in place. Without a GPU the staged path
 runs on the CPU with the state in the daemons' host tier.
 
-    python examples/train_offload.py [--gpu 0] [--bf16] [--steps 200]
+With --accum N every step sums N micro-batches' gradients in disaggregated memory too
+(models.OffloadedGradAccumulator: fp32 accumulators in the remote half, one one-sided
+accumulate per micro-batch) and hands the optimizer their mean.
+
+    python examples/train_offload.py [--gpu 0] [--bf16] [--steps 200] [--accum 4]
 """
 import argparse
 import os
@@ -17,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from oncilla_amd import api  # noqa: E402
-from oncilla_amd.models import OffloadedAdam  # noqa: E402
+from oncilla_amd.models import OffloadedAdam, OffloadedGradAccumulator  # noqa: E402
 from oncilla_amd.parallel import Mesh  # noqa: E402
 
 
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--daemons", type=int, default=3)
+    ap.add_argument("--accum", type=int, default=0, help="micro-batches per step, summed in disaggregated memory")
     args = ap.parse_args()
     on_gpu = args.gpu is not None
     dev = f"cuda:{args.gpu}" if on_gpu else "cpu"
@@ -40,17 +45,42 @@ def main():
             opt = OffloadedAdam(model.parameters(), c, lr=3e-3)
             tiers = sorted({e["tier"] for e in opt.allocs[0].remote_info()["extents"]})
             first = last = None
-            for step in range(args.steps):
+            params = list(model.parameters())
+            acc = OffloadedGradAccumulator(params, c) if args.accum > 0 else None
+
+            def micro_batch():
                 x = torch.randn(256, 64, device=dev)
                 with torch.no_grad():
                     y = teacher(x)
-                loss = torch.nn.functional.mse_loss(model(x.to(dtype)).float(), y)
-                opt.zero_grad()
-                loss.backward()
-                opt.step()
+                return torch.nn.functional.mse_loss(model(x.to(dtype)).float(), y)
+
+            for step in range(args.steps):
+                if acc:
+                    acc.zero()
+                    total = 0.0
+                    for _ in range(args.accum):
+                        loss = micro_batch()
+                        acc.zero_grads()
+                        loss.backward()
+                        acc.add(scale=1.0 / args.accum)  # remote fp32 += grad / N, one launch
+                        total += loss.item()
+                    sums = acc.read()
+                    with torch.no_grad():
+                        for p, g in zip(params, sums):
+                            p.grad.copy_(g)  # the mean gradient, rounded once into the parameter's dtype
+                    opt.step()
+                    step_loss = total / args.accum  # the step's loss: the mean over its micro-batches
+                else:
+                    loss = micro_batch()
+                    opt.zero_grad()
+                    loss.backward()
+                    opt.step()
+                    step_loss = loss.item()
                 if step == 0:
-                    first = loss.item()
-                last = loss.item()
+                    first = step_loss
+                last = step_loss
+            if acc:
+                acc.close()
             opt.close()
     where = "+".join({1: "host tier", 2: "peer HBM"}[t] for t in tiers)
     print(f"{args.steps} steps, mode={opt.mode}, {dtype}, optimizer state in {where}: "

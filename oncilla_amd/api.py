@@ -82,6 +82,18 @@ class OcmStridedParams(ctypes.Structure):
     ]
 
 
+class OcmAccParams(ctypes.Structure):
+    """struct ocm_acc_params (32 bytes)."""
+
+    _fields_ = [
+        ("local_offset", ctypes.c_uint64),
+        ("remote_offset", ctypes.c_uint64),
+        ("elems", ctypes.c_uint64),
+        ("dtype", ctypes.c_uint32),
+        ("scale", ctypes.c_float),
+    ]
+
+
 class OcmAllocParams(ctypes.Structure):
     """struct ocm_alloc_params (24 bytes)."""
 
@@ -191,6 +203,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_quant_bytes": (ctypes.c_size_t, [u64]),
             "ocm_copy_onesided_quant": (i32, [vp, ctypes.POINTER(OcmQuantParams), i32, i32]),
             "ocm_copy_onesided_strided": (i32, [vp, ctypes.POINTER(OcmStridedParams), i32, i32]),
+            "ocm_copy_onesided_accumulate": (i32, [vp, ctypes.POINTER(OcmAccParams), i32, i32]),
             "ocm_stream_wait": (i32, [vp, vp]),
             "ocm_plan_create": (vp, []),
             "ocm_plan_add": (i32, [vp, vp, ctypes.POINTER(OcmParams), i32]),
@@ -214,6 +227,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
             "ocm_x_pattern": (ctypes.c_longlong, [vp, u64, u64, ctypes.c_uint32, i32]),
             "ocm_x_counters": (None, [ctypes.POINTER(u64)]),
+            "ocm_x_acc_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_stats": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_health": (None, [ctypes.POINTER(u64)]),
             "ocm_x_tick_stats": (ctypes.c_int, [ctypes.POINTER(u64)]),
@@ -278,6 +292,10 @@ COUNTER_KEYS = ["n_put", "n_get", "bytes_put", "bytes_get", "n_alloc", "n_free",
 OCM_BATCH_ASYNC = 1
 OCM_QUANT_BF16 = 1
 OCM_QUANT_FP16 = 2
+OCM_ACC_F32 = 1
+OCM_ACC_BF16 = 2
+OCM_ACC_FP16 = 3
+ACC_COUNTER_KEYS = ["n_acc", "n_acc_ops", "bytes_acc"]
 
 
 class Plan:
@@ -404,6 +422,64 @@ def strided_ops(ops) -> BatchOps:
     b.keep = rec
     b.strided = True
     return b
+
+
+def acc_dtype(dtype) -> int:
+    """enum ocm_acc_dtype of a torch dtype, of "fp32" / "bf16" / "fp16", or of the enum value itself."""
+    if isinstance(dtype, int):
+        if dtype not in (OCM_ACC_F32, OCM_ACC_BF16, OCM_ACC_FP16):
+            raise ValueError(f"{dtype} is no ocm_acc_dtype value (1 fp32, 2 bf16, 3 fp16)")
+        return dtype
+    name = str(dtype).replace("torch.", "")
+    try:
+        return {"fp32": OCM_ACC_F32, "float32": OCM_ACC_F32, "float": OCM_ACC_F32, "bf16": OCM_ACC_BF16,
+                "bfloat16": OCM_ACC_BF16, "fp16": OCM_ACC_FP16, "float16": OCM_ACC_FP16, "half": OCM_ACC_FP16}[name]
+    except KeyError:
+        raise ValueError(f"accumulates take float32, bfloat16 or float16 elements, not {dtype}") from None
+
+
+def acc_ops(ops, dtype=None, scale: float = 1.0) -> BatchOps:
+    """Descriptor list for Allocation.accumulate_batch from an (n, 3) array (or rows)
+    [local_offset, remote_offset, elems], every op with `dtype` and `scale`; or from an (n, 5)
+    one whose columns 3 and 4 are each op's ocm_acc_dtype value and scale; `dtype` and `scale`
+    must then be left at their defaults (ValueError otherwise: they would be ignored). Built
+    once (no per-op Python objects)."""
+    import numpy as np
+
+    a = np.asarray(ops)
+    if a.ndim != 2 or a.shape[1] not in (3, 5):
+        if a.size == 0:
+            a = a.reshape(0, 3)
+        else:
+            raise ValueError("acc_ops takes an (n, 3) or an (n, 5) array")
+    n = int(a.shape[0])
+    rec = np.zeros(max(1, n), dtype=np.dtype([("lo", "<u8"), ("ro", "<u8"), ("el", "<u8"), ("dt", "<u4"), ("sc", "<f4")]))
+    if n:
+        ints = a[:, :3] if a.dtype == np.uint64 else a[:, :3].astype(np.int64)
+        rec["lo"][:n], rec["ro"][:n], rec["el"][:n] = ints[:, 0], ints[:, 1], ints[:, 2]
+        if a.shape[1] == 5:
+            if dtype is not None or scale != 1.0:
+                raise ValueError("acc_ops: an (n, 5) array carries each op's dtype and scale; pass neither beside it")
+            rec["dt"][:n] = a[:, 3].astype(np.int64)
+            with np.errstate(over="ignore"):
+                rec["sc"][:n] = a[:, 4].astype(np.float32)
+        else:
+            if dtype is None:
+                raise ValueError("acc_ops: an (n, 3) array needs a dtype")
+            rec["dt"][:n] = acc_dtype(dtype)
+            with np.errstate(over="ignore"):
+                rec["sc"][:n] = np.float32(scale)
+    b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmAccParams)), n)
+    b.keep = rec
+    b.acc = True
+    return b
+
+
+def acc_counters() -> dict:
+    """This process's accumulate counters (ocm_x_acc_counters): calls, ops, accumulator bytes."""
+    out = (ctypes.c_uint64 * len(ACC_COUNTER_KEYS))()
+    load().ocm_x_acc_counters(out)
+    return dict(zip(ACC_COUNTER_KEYS, [int(v) for v in out]))
 
 
 def set_tuning(variant: int = 0, blocks: int = 0, nontemporal: bool = True) -> None:
@@ -814,6 +890,21 @@ class Allocation:
             raise TypeError("quant_batch takes a quant_ops list, not a batch_ops one")
         if self._c.lib.ocm_copy_onesided_quant(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_quant: " + last_error())
+
+    def accumulate_batch(self, ops, dtype=None, scale: float = 1.0, async_: bool = False) -> None:
+        """One-sided accumulate in one launch (ocm_copy_onesided_accumulate): for every element of
+        every op, remote_f32[i] = remote_f32[i] + scale * local[i], as two fp32 roundings
+        (:func:`oncilla_amd.ops.accumulate_reference`). ``ops``: an (n, 3) array or rows
+        [local_offset, remote_offset, elems] with ``dtype`` and ``scale`` for all of them, an
+        (n, 5) one with a per-op dtype value and scale, or a prepared :func:`acc_ops` list; beside
+        either of the last two, ``dtype`` and ``scale`` must stay at their defaults (ValueError)."""
+        if isinstance(ops, BatchOps) and (dtype is not None or scale != 1.0):
+            raise ValueError("accumulate_batch: a prepared list carries each op's dtype and scale; pass neither beside it")
+        arr = ops if isinstance(ops, BatchOps) else acc_ops(ops, dtype, scale)
+        if not getattr(arr, "acc", False):
+            raise TypeError("accumulate_batch takes an acc_ops list, not a batch_ops, quant_ops or strided_ops one")
+        if self._c.lib.ocm_copy_onesided_accumulate(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
+            raise OcmError("ocm_copy_onesided_accumulate: " + last_error())
 
     def strided_batch(self, ops, async_: bool = False) -> None:
         """Strided one-sided ops in one launch (ocm_copy_onesided_strided): row r of an op moves
