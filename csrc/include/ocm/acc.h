@@ -1,10 +1,10 @@
 // One-sided accumulate (ocm_copy_onesided_accumulate): the remote half holds fp32
 // accumulators, the local half elements of ocm_acc_dtype, and every element becomes
 //     remote[i] = remote[i] + scale * widen(local[i]).
-// One launch serves a whole list, planned like a batch (ocm/xfer.h): the list is cut
-// into wave-tiles of kAccTileElems elements in op-relative coordinates (4 KiB of
-// accumulators), the host prefix-sums each op's tile count into `first_tile`, and
-// every wave walks a contiguous tile range.
+// One launch serves a whole list, planned as every descriptor list is (ocm/list.h): the
+// list is cut into wave-tiles of kAccTileElems elements in op-relative coordinates
+// (4 KiB of accumulators), the host prefix-sums each op's tile count into `first_tile`,
+// and every wave walks a contiguous tile range.
 //
 // The element rule is defined bit for bit, so that the kernel, the host path and the
 // torch oracle agree whatever the pair: two IEEE fp32 operations, each rounded to
@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "ocm/list.h"
 #include "oncillamem.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -116,12 +117,7 @@ inline void acc_pack(const struct ocm_acc_params &p, Op *o) {
 // Fills first_tile, returns total tiles.
 template <class Op>
 inline uint64_t acc_plan(Op *ops, uint32_t n) {
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        ops[i].first_tile = total;
-        total += acc_tile_count(ops[i].len);
-    }
-    return total;
+    return list_plan(ops, n, [](const Op &op) { return acc_tile_count(op.len); });
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)

@@ -17,9 +17,12 @@ namespace ocm {
 constexpr uint32_t kQuantTileShift = 11;  // 2048 elements: 4 KiB of source, 2 KiB of codes, 64 scale bytes
 constexpr uint32_t kQuantTileElems = 1u << kQuantTileShift;
 
+inline uint64_t quant_tile_count(uint64_t elems) { return (elems + kQuantTileElems - 1) >> kQuantTileShift; }
 // Fills first_tile, returns total tiles.
-uint64_t xfer_quant_plan(XferBatchOp *ops, uint32_t n);
-// a.grid from xfer_batch_grid, a.wave_op from xfer_batch_wave_ops (large lists).
+inline uint64_t xfer_quant_plan(XferBatchOp *ops, uint32_t n) {
+    return list_plan(ops, n, [](const XferBatchOp &op) { return quant_tile_count(op.len); });
+}
+// a.grid from xfer_batch_grid, a.wave_op from list_wave_ops (large lists).
 // Stores: nontemporal (t.nontemporal), except that puts into a pool wholly in the
 // pinned host tier (a.host_tier) store plain, as the batch kernel's host shape does.
 hipError_t xfer_quant_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream);

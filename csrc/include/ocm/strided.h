@@ -1,8 +1,8 @@
 // Strided one-sided ops (ocm_copy_onesided_strided): `rows` pieces of `row_bytes`,
 // one stride per side, between the linear side and the striped side. One launch
-// serves a whole list, planned like a batch (ocm/xfer.h): the list is cut into
-// wave-tiles, the host prefix-sums each op's tile count into `first_tile`, and every
-// wave walks a contiguous tile range. One descriptor per op is all the kernel reads:
+// serves a whole list, planned as every descriptor list is (ocm/list.h): the list is
+// cut into wave-tiles, the host prefix-sums each op's tile count into `first_tile`, and
+// every wave walks a contiguous tile range. One descriptor per op is all the kernel reads:
 // nothing grows with the number of rows.
 //
 // Tiles are cut in row-relative coordinates: piece k of a row is its bytes
@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "ocm/list.h"
 #include "oncillamem.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -164,24 +165,10 @@ struct XferStridedArgs {
 
 // Host-side plan: fills tiles_per_row and first_tile, returns total tiles.
 inline uint64_t xfer_strided_plan(XferStridedOp *ops, uint32_t n, uint32_t tile_shift) {
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        ops[i].tiles_per_row = strided_tiles_per_row(ops[i].row_bytes, tile_shift);
-        ops[i].first_tile = total;
-        total += strided_tile_count(ops[i]);
-    }
-    return total;
-}
-// wave_op[w] for every wave of `grid` workgroups (4 * grid entries), as xfer_batch_wave_ops.
-inline void xfer_strided_wave_ops(const XferStridedOp *ops, uint32_t n, uint64_t total_tiles, uint32_t grid, uint32_t *out) {
-    const uint64_t waves = (uint64_t)grid * 4;
-    const uint64_t per = (total_tiles + waves - 1) / waves;
-    uint32_t i = 0;
-    for (uint64_t w = 0; w < waves; w++) {
-        const uint64_t t = w * per;
-        while (i + 1 < n && ops[i + 1].first_tile <= t) i++;
-        out[w] = i;
-    }
+    return list_plan(ops, n, [tile_shift](XferStridedOp &op) {
+        op.tiles_per_row = strided_tiles_per_row(op.row_bytes, tile_shift);
+        return strided_tile_count(op);
+    });
 }
 
 }  // namespace ocm

@@ -15,6 +15,8 @@
 
 #include <cstdint>
 
+#include "ocm/list.h"
+
 namespace ocm {
 
 constexpr int kXferMaxExtents = 8;
@@ -93,11 +95,10 @@ XferTuning xfer_tuning_from_env();
 
 // ---- batched one-sided ops (scatter/gather lists) ----
 // Many ops on one remote pair in ONE launch. The batch is cut into 4 KiB
-// wave-tiles (smaller when the stripe unit is): the host prefix-sums each op's
-// tile count into `first_tile`, sizes the grid, and gives every wave a
-// contiguous tile range plus the op its first tile belongs to (`wave_op`), so
-// waves never search; they walk forward through the ops they cover. Small
-// batches travel in the kernel arguments, large ones in a device buffer.
+// wave-tiles (smaller when the stripe unit is) and planned as every descriptor
+// list is (ocm/list.h): `first_tile` by prefix sum, a contiguous tile range per
+// wave, and `wave_op`, the op each wave starts in. Small batches travel in the
+// kernel arguments, large ones in a device buffer.
 struct XferBatchOp {
     uint64_t lin_off;     // offset in the linear buffer
     uint64_t rem_off;     // offset in striped coordinates
@@ -127,13 +128,15 @@ struct XferBatchArgs {
     XferBatchOp inline_ops[kXferInlineOps];
 };
 
-// Host-side plan. Fills first_tile, returns total tiles.
-uint64_t xfer_batch_plan(XferBatchOp *ops, uint32_t n, uint32_t tile_shift);
+// Host-side plan. Fills first_tile, returns total tiles (an empty op has none).
+inline uint64_t xfer_batch_plan(XferBatchOp *ops, uint32_t n, uint32_t tile_shift) {
+    return list_plan(ops, n, [tile_shift](const XferBatchOp &op) {
+        return op.len ? xfer_tile_count(op.rem_off, op.len, tile_shift) : 0;
+    });
+}
 // Workgroups for `total_tiles` (4 waves each, capped for residency; host-tier
 // batches are capped lower, OCM_BATCH_HOST_GRID: PCIe wants fewer streams).
 uint32_t xfer_batch_grid(uint64_t total_tiles, bool host_tier = false);
-// wave_op[w] for every wave of `grid` workgroups (4 * grid entries).
-void xfer_batch_wave_ops(const XferBatchOp *ops, uint32_t n, uint64_t total_tiles, uint32_t grid, uint32_t *out);
 // tile shift for a remote layout: 4 KiB wave-tiles, or the stripe unit when smaller.
 uint32_t xfer_batch_tile_shift(uint32_t n_ext, uint32_t unit_shift);
 hipError_t xfer_batch_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream);
@@ -144,12 +147,12 @@ hipError_t xfer_batch_graph_node(hipGraph_t graph, hipGraphNode_t dep, const Xfe
                                  hipGraphNode_t *node);
 
 // Strided lists (ocm/strided.h: the descriptors, the tile geometry and the host plan):
-// one launch; a.grid from xfer_batch_grid, a.wave_op from xfer_strided_wave_ops.
+// one launch; a.grid from xfer_batch_grid, a.wave_op from list_wave_ops.
 struct XferStridedArgs;
 hipError_t xfer_strided_launch(const XferStridedArgs &a, const XferTuning &t, hipStream_t stream);
 
 // Accumulate lists (ocm/acc.h: the element rule, the tile count and the descriptor
-// packing): one launch; a.grid from xfer_batch_grid, a.wave_op from xfer_batch_wave_ops.
+// packing): one launch; a.grid from xfer_batch_grid, a.wave_op from list_wave_ops.
 // Stores are nontemporal (t.nontemporal), plain into a pool wholly in the pinned host tier.
 hipError_t xfer_acc_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream);
 

@@ -128,33 +128,27 @@ __device__ __forceinline__ void acc_tile_any(const XferBatchArgs &a, const char 
         acc_tile<DT, NT, false>(a, lin, rem, nv, scale, lane);
 }
 
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
-
 template <bool NT>
 __global__ __launch_bounds__(kThreads) void xfer_acc_kernel(XferBatchArgs a) {
     // wave index, made scalar: everything below but the lane's own vectors is wave-uniform
     const uint32_t wl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wl);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t waves = (uint64_t)a.grid * kWaves;
-    const uint64_t per = (a.total_tiles + waves - 1) / waves;
-    uint64_t t = (uint64_t)w * per;
-    const uint64_t t1 = t + per < a.total_tiles ? t + per : a.total_tiles;
+    uint64_t t, t1;
+    list_wave_range(w, a.grid, a.total_tiles, &t, &t1);
     if (t >= t1) return;
-    const bool inl = a.n_ops <= (uint32_t)kXferInlineOps;
-    const XferBatchOp *ops = inl ? a.inline_ops : a.ops;
-    uint32_t i = inl ? 0u : a.wave_op[w];
+    const XferBatchOp *ops;
+    uint32_t i = list_wave_start(a, w, &ops);
     for (; t < t1; t++) {
-        while (i + 1 < a.n_ops && uni64(ops[i + 1].first_tile) <= t) i++;
+        while (i + 1 < a.n_ops && uniform64(ops[i + 1].first_tile) <= t) i++;
         const XferBatchOp &op = ops[i];
         // the descriptor's fields, made scalar (ops[] may be read with vector loads)
-        const uint32_t elems = uni32((uint32_t)op.len), dtype = uni32(op.pad);
-        const uint64_t lin_off = uni64(op.lin_off), rem_off = uni64(op.rem_off);
-        const uint32_t e0 = uni32((uint32_t)(t - op.first_tile)) << kAccTileShift;  // elems < 2^31
+        const uint32_t elems = uniform32((uint32_t)op.len), dtype = uniform32(op.pad);
+        const uint64_t lin_off = uniform64(op.lin_off), rem_off = uniform64(op.rem_off);
+        const uint32_t e0 = uniform32((uint32_t)(t - op.first_tile)) << kAccTileShift;  // elems < 2^31
         const uint32_t left = elems - e0;
         const uint32_t nv = (left < kAccTileElems ? left : kAccTileElems) >> 2;
-        const float scale = acc_bits_float(uni32(op.put));
+        const float scale = acc_bits_float(uniform32(op.put));
         const uint64_t rem = rem_off + 4ull * e0;
         const char *lin = a.lin + lin_off;
         if (dtype == kAccF32)
@@ -170,9 +164,7 @@ __global__ __launch_bounds__(kThreads) void xfer_acc_kernel(XferBatchArgs a) {
 
 hipError_t xfer_acc_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || a.grid == 0 || a.abs_lin) return hipErrorInvalidValue;
-    if (a.n_ext > 1 && a.unit_shift < 4) return hipErrorInvalidValue;  // a 16-byte vector must fit a unit
-    if (a.n_ops > (uint32_t)kXferInlineOps && !(a.ops && a.wave_op)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<true, true>(a, kXferInlineOps)) return hipErrorInvalidValue;
     const bool nt = t.nontemporal && !a.host_tier;
     hipLaunchKernelGGL(nt ? xfer_acc_kernel<true> : xfer_acc_kernel<false>, dim3(a.grid), dim3(kThreads), 0, stream, a);
     return hipGetLastError();

@@ -28,14 +28,11 @@ template <bool NT, bool HOST = false>
 __global__ __launch_bounds__(kThreads) void xfer_batch_kernel(XferBatchArgs a) {
     // wave index, made scalar: everything below is wave-uniform
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
-    const uint64_t waves = (uint64_t)a.grid * kWaves;
-    const uint64_t per = (a.total_tiles + waves - 1) / waves;
-    uint64_t t = (uint64_t)w * per;
-    const uint64_t t1 = t + per < a.total_tiles ? t + per : a.total_tiles;
+    uint64_t t, t1;
+    list_wave_range(w, a.grid, a.total_tiles, &t, &t1);
     if (t >= t1) return;
-    const bool inl = a.n_ops <= (uint32_t)kXferInlineOps;
-    const XferBatchOp *ops = inl ? a.inline_ops : a.ops;
-    uint32_t i = inl ? 0u : a.wave_op[w];
+    const XferBatchOp *ops;
+    uint32_t i = list_wave_start(a, w, &ops);
     for (; t < t1; t++) {
         while (i + 1 < a.n_ops && ops[i + 1].first_tile <= t) i++;
         const XferBatchOp &op = ops[i];
@@ -62,25 +59,10 @@ BatchKernel batch_kernel_for(const XferBatchArgs &a, const XferTuning &t) {
     return t.nontemporal ? xfer_batch_kernel<true> : xfer_batch_kernel<false>;
 }
 
-// Whether a batch with something to copy can be launched.
-bool batch_args_valid(const XferBatchArgs &a) {
-    if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || a.grid == 0) return false;
-    return a.n_ops <= (uint32_t)kXferInlineOps || (a.ops && a.wave_op);
-}
-
 }  // namespace
 
 uint32_t xfer_batch_tile_shift(uint32_t n_ext, uint32_t unit_shift) {
     return (n_ext > 1 && unit_shift < kBatchTileShift) ? unit_shift : kBatchTileShift;
-}
-
-uint64_t xfer_batch_plan(XferBatchOp *ops, uint32_t n, uint32_t tile_shift) {
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        ops[i].first_tile = total;
-        if (ops[i].len) total += xfer_tile_count(ops[i].rem_off, ops[i].len, tile_shift);
-    }
-    return total;
 }
 
 uint32_t xfer_batch_grid(uint64_t total_tiles, bool host_tier) {
@@ -94,20 +76,9 @@ uint32_t xfer_batch_grid(uint64_t total_tiles, bool host_tier) {
     return (uint32_t)(want < cap ? (want ? want : 1) : cap);
 }
 
-void xfer_batch_wave_ops(const XferBatchOp *ops, uint32_t n, uint64_t total_tiles, uint32_t grid, uint32_t *out) {
-    const uint64_t waves = (uint64_t)grid * kWaves;
-    const uint64_t per = (total_tiles + waves - 1) / waves;
-    uint32_t i = 0;
-    for (uint64_t w = 0; w < waves; w++) {
-        const uint64_t t = w * per;
-        while (i + 1 < n && ops[i + 1].first_tile <= t) i++;
-        out[w] = i;
-    }
-}
-
 hipError_t xfer_batch_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (!batch_args_valid(a)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<false, false>(a, kXferInlineOps)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(batch_kernel_for(a, t), dim3(a.grid), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
@@ -116,7 +87,7 @@ hipError_t xfer_batch_graph_node(hipGraph_t graph, hipGraphNode_t dep, const Xfe
                                  hipGraphNode_t *node) {
     const size_t ndep = dep ? 1 : 0;
     if (a.total_tiles == 0 || a.n_ops == 0) return hipGraphAddEmptyNode(node, graph, dep ? &dep : nullptr, ndep);
-    if (!batch_args_valid(a)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<false, false>(a, kXferInlineOps)) return hipErrorInvalidValue;
     // Parameters by address: `a` must outlive the graph (the plan's stage
     // storage), whether or not the runtime copies them into the node.
     void *params[] = {const_cast<XferBatchArgs *>(&a)};

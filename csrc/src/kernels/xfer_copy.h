@@ -1,9 +1,10 @@
-// Device-side primitives shared by the transfer kernels (xfer.hip, xfer_batch.hip,
-// xfer_service.hip): the one copy loop, tile geometry, and the release / publish
-// hand-off. Device only: include from a HIP translation unit, inside no namespace.
+// Device-side primitives shared by the transfer kernels (xfer.hip, xfer_service.hip and
+// the list kernels xfer_batch / _quant / _strided / _acc.hip): the one copy loop, tile
+// geometry, how a wave enters a descriptor list, and the release / publish hand-off. Device only: include from a HIP translation unit, inside no namespace.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ocm/list.h"
 #include "ocm/xfer.h"
 
 namespace ocm {
@@ -16,6 +17,7 @@ constexpr int kThreads = 256;
 constexpr int kUnroll = 8;                                    // 8 x 16 B in flight per lane
 constexpr uint32_t kTileShift = 15;                           // 32 KiB tiles = 256 lanes x 16 B x 8
 constexpr int kWaves = kThreads / 64;
+static_assert(kWaves == kListWaves, "the host plans lists for workgroups of kListWaves waves");
 
 // Store flavours of the copy loops:
 //   ST_PLAIN  plain stores (cached in the XCD's L2);
@@ -269,6 +271,32 @@ __device__ __forceinline__ TileSpan tile_span_of(const E &x, uint32_t n_ext, uin
 
 __device__ __forceinline__ TileSpan tile_span(const XferArgs &a, uint64_t ti, uint64_t first_tile) {
     return tile_span_of(a, a.n_ext, a.unit_shift, a.tile_shift, a.lin, a.rem_off, a.len, a.put, ti, first_tile);
+}
+
+// ---- descriptor lists (ocm/list.h) ----
+// A value every lane holds alike, moved to scalar registers. A list's descriptors are
+// read through a pointer that is the kernel arguments or device memory (a generic
+// pointer, whose loads the compiler takes for per-lane values): this states what they are.
+__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    return ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32) | uniform32((uint32_t)v);
+}
+
+// How a wave with tiles enters the list of launch arguments `a`. Every list kernel opens with
+//     uint64_t t, t1;
+//     list_wave_range(w, a.grid, a.total_tiles, &t, &t1);   (ocm/list.h; w wave-uniform)
+//     if (t >= t1) return;
+//     const Op *ops;
+//     uint32_t i = list_wave_start(a, w, &ops);
+// *ops: the descriptors, in the kernel arguments for a list of at most the inline
+// capacity, else in device memory. Returns the op to start the walk from. (The early
+// return stays in the kernel: folded in here, the merge after it kept one instantiation
+// from reading the arguments in place, and it copied all 2 KiB of them to scratch.)
+template <class Args, class Op>
+__device__ __forceinline__ uint32_t list_wave_start(const Args &a, uint32_t w, const Op **ops) {
+    const bool inl = a.n_ops <= (uint32_t)(sizeof(Args::inline_ops) / sizeof(Op));
+    *ops = inl ? a.inline_ops : a.ops;
+    return inl ? 0u : a.wave_op[w];
 }
 
 // Drain every wave's stores into L2, join the workgroup, then ONE system-scope

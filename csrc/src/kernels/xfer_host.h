@@ -5,6 +5,8 @@
 
 #include <cstdlib>
 
+#include "ocm/xfer.h"
+
 namespace ocm::kernels {
 
 __attribute__((visibility("hidden"))) inline int env_int(const char *k, int dflt) {
@@ -22,6 +24,20 @@ __attribute__((visibility("hidden"))) inline int num_cus() {
     else
         cus = 256;
     return cus;
+}
+
+// Whether a descriptor list with something to do can be launched (batch, converting,
+// strided and accumulate lists alike): `inline_cap` ops travel in the kernel arguments,
+// a longer list needs its device copy and wave table. UNIT16: the kernel maps 16-byte
+// vectors through the extents one by one, so a vector must fit a stripe unit.
+// NO_ABS_LIN: the kernel reads op.lin_off as an offset only.
+template <bool UNIT16, bool NO_ABS_LIN, class Args>
+inline bool list_args_valid(const Args &a, int inline_cap) {
+    if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || a.grid == 0) return false;
+    if (UNIT16 && a.n_ext > 1 && a.unit_shift < 4) return false;
+    if constexpr (NO_ABS_LIN)
+        if (a.abs_lin) return false;
+    return a.n_ops <= (uint32_t)inline_cap || (a.ops && a.wave_op);
 }
 
 }  // namespace ocm::kernels

@@ -146,14 +146,11 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_kernel(XferBatchArgs a) {
     const uint32_t wl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wl);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t waves = (uint64_t)a.grid * kWaves;
-    const uint64_t per = (a.total_tiles + waves - 1) / waves;
-    uint64_t t = (uint64_t)w * per;
-    const uint64_t t1 = t + per < a.total_tiles ? t + per : a.total_tiles;
+    uint64_t t, t1;
+    list_wave_range(w, a.grid, a.total_tiles, &t, &t1);
     if (t >= t1) return;
-    const bool inl = a.n_ops <= (uint32_t)kXferInlineOps;
-    const XferBatchOp *ops = inl ? a.inline_ops : a.ops;
-    uint32_t i = inl ? 0u : a.wave_op[w];
+    const XferBatchOp *ops;
+    uint32_t i = list_wave_start(a, w, &ops);
     for (; t < t1; t++) {
         while (i + 1 < a.n_ops && ops[i + 1].first_tile <= t) i++;
         const XferBatchOp &op = ops[i];
@@ -179,20 +176,9 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_kernel(XferBatchArgs a) {
 
 }  // namespace
 
-uint64_t xfer_quant_plan(XferBatchOp *ops, uint32_t n) {
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        ops[i].first_tile = total;
-        total += (ops[i].len + kQuantTileElems - 1) >> kQuantTileShift;
-    }
-    return total;
-}
-
 hipError_t xfer_quant_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || a.grid == 0 || a.abs_lin) return hipErrorInvalidValue;
-    if (a.n_ext > 1 && a.unit_shift < 4) return hipErrorInvalidValue;  // a 16-byte vector must fit a unit
-    if (a.n_ops > (uint32_t)kXferInlineOps && !(a.ops && a.wave_op)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<true, true>(a, kXferInlineOps)) return hipErrorInvalidValue;
     const bool nt = t.nontemporal && !a.host_tier;
     hipLaunchKernelGGL(nt ? xfer_quant_kernel<true> : xfer_quant_kernel<false>, dim3(a.grid), dim3(kThreads), 0, stream, a);
     return hipGetLastError();

@@ -42,14 +42,7 @@ __device__ __forceinline__ void copy_piece(const XferStridedArgs &a, const Strid
     }
 }
 
-// A value every lane holds alike, moved to scalar registers. The descriptors are read
-// through a pointer that is the kernel arguments or device memory (a generic pointer,
-// whose loads the compiler takes for per-lane values): this states what they are.
-__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    return ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32) | uniform32((uint32_t)v);
-}
-
+// The descriptor of an op, in scalar registers (uniform32 / uniform64, xfer_copy.h).
 __device__ __forceinline__ XferStridedOp load_op(const XferStridedOp *p) {
     XferStridedOp o;
     o.lin_off = uniform64(p->lin_off);
@@ -68,15 +61,12 @@ template <bool NT, bool HOST>
 __global__ __launch_bounds__(kThreads) void xfer_strided_kernel(XferStridedArgs a) {
     // wave index, made scalar: everything below but the lane's own vectors is wave-uniform
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
-    const uint64_t waves = (uint64_t)a.grid * kWaves;
-    const uint64_t per = (a.total_tiles + waves - 1) / waves;
-    uint64_t t = (uint64_t)w * per;
-    const uint64_t t1 = t + per < a.total_tiles ? t + per : a.total_tiles;
+    uint64_t t, t1;
+    list_wave_range(w, a.grid, a.total_tiles, &t, &t1);
     if (t >= t1) return;
-    const bool inl = a.n_ops <= (uint32_t)kStridedInlineOps;
-    const XferStridedOp *ops = inl ? a.inline_ops : a.ops;
-    uint32_t i = inl ? 0u : a.wave_op[w];
-    XferStridedOp op;        // the op of tile t, in scalar registers
+    const XferStridedOp *ops;
+    uint32_t i = list_wave_start(a, w, &ops);
+    XferStridedOp op;       // the op of tile t, in scalar registers
     uint64_t next = 0;       // first tile of the op after it (none: past every tile)
     uint64_t row = 0, k = 0; // tile t is piece k of row `row`
     for (; t < t1; t++) {
@@ -106,10 +96,9 @@ __global__ __launch_bounds__(kThreads) void xfer_strided_kernel(XferStridedArgs 
 
 hipError_t xfer_strided_launch(const XferStridedArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || a.grid == 0 || !a.lin) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<false, false>(a, kStridedInlineOps) || !a.lin) return hipErrorInvalidValue;
     // a tile is at most one stripe unit (two spans a tile at the most)
     if (a.tile_shift > 63 || (a.n_ext > 1 && a.tile_shift > a.unit_shift)) return hipErrorInvalidValue;
-    if (a.n_ops > (uint32_t)kStridedInlineOps && !(a.ops && a.wave_op)) return hipErrorInvalidValue;
     auto kernel = a.host_tier    ? xfer_strided_kernel<true, true>
                   : t.nontemporal ? xfer_strided_kernel<true, false>
                                   : xfer_strided_kernel<false, false>;

@@ -550,26 +550,7 @@ void push_release();
 // An address of extent e valid on device `dev` (its owner's GPU), opening its slab there once.
 char *extent_view(const Extent &e, int dev);
 
-// ---- batches (batch.cpp)
-// What run_list needs of a descriptor list, whatever its kind (batch, converting, strided).
-struct BatchList {
-    const void *desc = nullptr;  // the planned descriptors (host)
-    size_t desc_bytes = 0;
-    bool large = false;          // more descriptors than travel in the kernel arguments: upload them
-    uint32_t grid = 0;           // workgroups; the wave table has 4 entries for each
-    bool count_launch = false;   // counts in n_batch_launches
-    void *ctx = nullptr;         // the caller's launch arguments, handed to both functions
-    void (*wave_ops)(void *ctx, uint32_t *out) = nullptr;  // fills the wave table (large lists)
-    hipError_t (*launch)(void *ctx, const void *dev_desc, const uint32_t *dev_wave, hipStream_t st) = nullptr;
-};
-int run_list(lib_alloc *a, const BatchList &list, bool async);
-// Which launch reads a list of XferBatchOp records.
-enum ListKind : int { LIST_BATCH = 0, LIST_QUANT = 1, LIST_ACC = 2 };
-int run_batch(lib_alloc *a, XferBatchArgs &args, std::vector<XferBatchOp> &v, bool async, int kind = LIST_BATCH);
-bool batch_device_path(const lib_alloc *a);
-void batch_layout_args(lib_alloc *a, bool abs_lin, XferBatchArgs *args);
-// Copy absolute device ranges (op.lin_off = address) into dst's remote half, one launch.
-int batch_put_abs(lib_alloc *dst, std::vector<XferBatchOp> &v);
+// ---- descriptor lists (batches and their kin): lists.h
 
 // ---- network tier (net.cpp)
 void net_drop(const std::string &ep);

@@ -15,7 +15,7 @@
 // copy_in/out (:491-499), swapped GPU->RMA offsets (:654).
 #include <cmath>
 
-#include "internal.h"
+#include "lists.h"
 #include "ocm/affinity.h"
 #include "ocm/optim.h"
 #include "ocm/stackdump.h"
@@ -1351,23 +1351,18 @@ int ocm_x_batch(int device, void *lin, void **ext, int n_ext, uint64_t unit, con
         v[i].len = ops[4 * i + 2];
         v[i].put = ops[4 * i + 3] != 0;
     }
-    args.n_ops = (uint32_t)n_ops;
-    args.total_tiles = xfer_batch_plan(v.data(), (uint32_t)n_ops, args.tile_shift);
+    list_plan_args(&args, v, xfer_batch_plan);  // as ocm_copy_onesided_batch plans
     if (!args.total_tiles) return 0;
-    args.grid = xfer_batch_grid(args.total_tiles);
     void *dev = nullptr;
-    if (n_ops <= kXferInlineOps) {
-        std::memcpy(args.inline_ops, v.data(), v.size() * sizeof(XferBatchOp));
-    } else {
-        const size_t dbytes = v.size() * sizeof(XferBatchOp), need = dbytes + (size_t)args.grid * 16;
+    if (n_ops > kXferInlineOps) {
+        const size_t need = list_upload_bytes<XferBatchOp>(v.size(), args.grid);
         std::vector<char> up(need);
-        std::memcpy(up.data(), v.data(), dbytes);
-        xfer_batch_wave_ops(v.data(), (uint32_t)n_ops, args.total_tiles, args.grid,
-                            reinterpret_cast<uint32_t *>(up.data() + dbytes));
-        if (hipMalloc(&dev, need) != hipSuccess || hipMemcpy(dev, up.data(), need, hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMalloc(&dev, need) != hipSuccess) return -1;
+        list_pack(&args, v, up.data(), dev);
+        if (hipMemcpy(dev, up.data(), need, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dev);
             return -1;
-        args.ops = static_cast<const XferBatchOp *>(dev);
-        args.wave_op = reinterpret_cast<const uint32_t *>(static_cast<char *>(dev) + dbytes);
+        }
     }
     XferTuning t = xfer_tuning_from_env();
     int rc = 0;

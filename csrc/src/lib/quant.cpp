@@ -3,11 +3,13 @@
 // half takes one kernel launch per list (ocm/quant.h), ordered like a batch; a
 // host local half (a CPU app, OCM_REMOTE_RDMA / _RMA pairs, the network tier)
 // encodes and decodes on this thread and moves each record with xfer().
-#include "internal.h"
+#include "lists.h"
 #include "ocm/mx8.h"
 
 using namespace ocm;
 using namespace ocmlib;
+
+static const ListNames kQuant = {"ocm_copy_onesided_quant", "converting one-sided copies", "ocm_quant", "quant", true};
 
 // Every op against the pair and the format's constraints. Adds to *src / *wire.
 static int check_quant_ops(lib_alloc *a, const struct ocm_quant_params *ops, int n_ops, uint64_t *src, uint64_t *wire) {
@@ -62,22 +64,12 @@ static int quant_host(lib_alloc *a, const struct ocm_quant_params *ops, int n_op
 
 static int quant_impl(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags, uint64_t *src,
                       uint64_t *wire) {
-    State &s = S();
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    if (!a || (!ops && n_ops)) OCM_FAIL(-1, "ocm_copy_onesided_quant: NULL argument");
-    if (!s.allocs.count(a)) OCM_FAIL(-1, "ocm_copy_onesided_quant: unknown allocation");
-    if (!a->remote) OCM_FAIL(-1, "converting one-sided copies need a remote pair (kind %d)", (int)a->kind);
-    if (n_ops < 0) OCM_FAIL(-1, "ocm_copy_onesided_quant: n_ops < 0");
-    if (check_quant_ops(a, ops, n_ops, src, wire) != 0) return -1;
-    if (n_ops == 0 || *src == 0) return 0;
-    if (!batch_device_path(a)) {
-        if (a->loc == LOC_DEVICE)
-            OCM_FAIL(-1, "ocm_copy_onesided_quant: a device local half needs every extent reachable by a kernel "
-                         "(no network tier, stripe unit >= 16 bytes)");
-        return quant_host(a, ops, n_ops);
-    }
-    DeviceGuard guard(s.device);
-    XferBatchArgs args;
+    std::unique_lock<std::recursive_mutex> lk;
+    const int path = list_enter(kQuant, lk, a, ops, n_ops,
+                                [&] { return check_quant_ops(a, ops, n_ops, src, wire) != 0 ? -1 : *src != 0; });
+    if (path <= PATH_NONE) return path;
+    if (path == PATH_HOST) return quant_host(a, ops, n_ops);
+    DeviceGuard guard(S().device);
     std::vector<XferBatchOp> v((size_t)n_ops, XferBatchOp{});
     for (int i = 0; i < n_ops; i++) {
         v[i].lin_off = ops[i].local_offset;
@@ -86,13 +78,9 @@ static int quant_impl(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_o
         v[i].put = ops[i].op_flag != 0;
         v[i].pad = ops[i].dtype;
     }
-    batch_layout_args(a, false, &args);
-    args.tile_shift = kQuantTileShift;
-    args.n_ops = (uint32_t)v.size();
-    args.total_tiles = xfer_quant_plan(v.data(), (uint32_t)v.size());
-    args.grid = xfer_batch_grid(args.total_tiles, args.host_tier != 0);
-    if (v.size() <= (size_t)kXferInlineOps) std::memcpy(args.inline_ops, v.data(), v.size() * sizeof(XferBatchOp));
-    return run_batch(a, args, v, (flags & OCM_BATCH_ASYNC) != 0, LIST_QUANT);
+    XferBatchArgs args;
+    list_fill_args(a, v, kQuantTileShift, [](XferBatchOp *o, uint32_t n, uint32_t) { return xfer_quant_plan(o, n); }, &args);
+    return run_list(a, args, v, xfer_quant_launch, (flags & OCM_BATCH_ASYNC) != 0);
 }
 
 extern "C" {
@@ -100,20 +88,14 @@ extern "C" {
 size_t ocm_quant_bytes(uint64_t elems) { return mx8_record_bytes(elems); }
 
 int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags) {
-    TraceRange tr("ocm_quant");
-    const uint64_t t0 = now_ns();
     uint64_t src = 0, wire = 0;
-    const int rc = quant_impl(a, ops, n_ops, flags, &src, &wire);
-    const uint64_t t1 = now_ns();
-    if (rc == 0) {
-        OpCounters &c = S().ctr;
-        c.n_quant++;
-        c.n_quant_ops += (uint64_t)n_ops;
-        c.bytes_quant_src += src;
-        c.bytes_quant_wire += wire;
-    }
-    trace_op("quant", wire, t0, t1, rc);
-    return rc;
+    return list_call(kQuant, wire, [&] { return quant_impl(a, ops, n_ops, flags, &src, &wire); },
+                     [&](OpCounters &c, uint64_t) {
+                         c.n_quant++;
+                         c.n_quant_ops += (uint64_t)n_ops;
+                         c.bytes_quant_src += src;
+                         c.bytes_quant_wire += wire;
+                     });
 }
 
 }  // extern "C"

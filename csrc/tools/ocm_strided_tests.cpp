@@ -148,7 +148,7 @@ void test_plan() {
     for (size_t i = 0; i < v.size(); i++) CHECK(v[i].first_tile == want_first[i], "first_tile of op %zu", i);
     for (uint32_t grid : {1u, 2u, 3u, 5u}) {
         std::vector<uint32_t> w(grid * 4);
-        xfer_strided_wave_ops(v.data(), (uint32_t)v.size(), total, grid, w.data());
+        list_wave_ops(v.data(), (uint32_t)v.size(), total, grid, w.data());
         const uint64_t per = (total + grid * 4 - 1) / (grid * 4);
         for (uint32_t k = 0; k < grid * 4; k++) {
             const uint64_t t = k * per;

@@ -49,11 +49,28 @@ def test_sixty_op_list(mesh_factory, n_daemons, async_):
         a.free()
 
 
+def _sizes_with_empties(n_ops, most):
+    # ops of no elements have no tiles: first, last, two in a row and between the others
+    return [0 if i in (0, 3, 4, n_ops - 1) or i % 9 == 8 else 4 * (1 + (i * 61) % most) for i in range(n_ops)]
+
+
 @pytest.mark.parametrize("n_ops", [7, 53])  # in the kernel arguments; uploaded, with a wave table
 @pytest.mark.parametrize("n_daemons", N_DAEMONS)
 def test_empty_ops_among_others(mesh_factory, n_daemons, n_ops):
-    # ops of no elements have no tiles: first, last, two in a row and between the others
-    sizes = [0 if i in (0, 3, 4, n_ops - 1) or i % 9 == 8 else 4 * (1 + (i * 61) % 400) for i in range(n_ops)]
+    _run_sized_list(mesh_factory, n_daemons, _sizes_with_empties(n_ops, 400))
+
+
+@pytest.mark.parametrize("n_ops", [48, 49])  # the most ops the kernel arguments hold, and one more
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_list_at_the_inline_capacity(mesh_factory, n_daemons, n_ops):
+    sizes = _sizes_with_empties(n_ops, 375)  # 4 to 1500 elements: one tile or two
+    sizes[1], sizes[2] = 4, 1500
+    assert max(sizes) == 1500 and min(s for s in sizes if s) == 4 and sizes.count(0) >= 4
+    _run_sized_list(mesh_factory, n_daemons, sizes)
+
+
+def _run_sized_list(mesh_factory, n_daemons, sizes):
+    n_ops = len(sizes)
     slot, rslot, dtype = 4096, 2 * UNIT, torch.bfloat16  # bytes per op in the local and in the remote half (<= 1600 elements)
     with _client(mesh_factory, n_daemons) as c:
         stage = n_ops * slot

@@ -67,6 +67,47 @@ def test_sixty_op_list(mesh_factory, n_daemons, dtype):
         a.free()
 
 
+@pytest.mark.parametrize("n_ops", [48, 49])  # the most ops the kernel arguments hold, and one more
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_list_at_the_inline_capacity(mesh_factory, n_daemons, n_ops):
+    dtype = torch.bfloat16
+    # 32 to 96 elements; ops of no elements first, last and two in a row; every third op a get
+    sizes = [0 if i in (0, 5, 6, n_ops - 1) else 32 * (1 + i % 3) for i in range(n_ops)]
+    lslot, rslot = 192, 128           # bytes per op in the local and in the remote half
+    stage, base = n_ops * lslot, UNIT - 64  # the records cross two stripe-unit boundaries
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, stage + n_ops * rslot, 4 * UNIT)
+        local = torch.full((stage,), 0x5A, dtype=torch.uint8)
+        remote = torch.full((n_ops * rslot,), 0xA5, dtype=torch.uint8)
+        rows, elems = [], {}
+        for i, n in enumerate(sizes):
+            put, lo, ro = i % 3 != 1, i * lslot, i * rslot
+            rows.append([int(put), lo, base + ro, n])
+            if n:
+                elems[i] = x = random_elems(n, dtype, seed=500 + i)
+                if put:
+                    local[lo:lo + 2 * n] = x.view(torch.uint8)
+                else:
+                    remote[ro:ro + api.quant_bytes(n)] = mx8_record_reference(x)
+        want_local, want_remote = local.clone(), remote.clone()
+        for i, x in elems.items():
+            put, lo, ro, n = rows[i][0], i * lslot, i * rslot, sizes[i]
+            if put:
+                want_remote[ro:ro + api.quant_bytes(n)] = mx8_record_reference(x)
+            else:
+                want_local[lo:lo + 2 * n] = roundtrip(x).view(torch.uint8)
+        assert {r[0] for r in rows if r[3]} == {0, 1}
+        write_remote(a, stage, base, remote)
+        write_local(a, 0, local)
+        before = api.counters()
+        a.quant_batch(np.array(rows), dtype)
+        after = api.counters()
+        assert after["n_quant"] == before["n_quant"] + 1 and after["n_quant_ops"] == before["n_quant_ops"] + n_ops
+        assert torch.equal(read_local(a, 0, stage), want_local)
+        assert torch.equal(read_remote(a, stage, base, n_ops * rslot), want_remote)
+        a.free()
+
+
 @pytest.mark.parametrize("n_daemons", N_DAEMONS)
 def test_host_path_records_match_kernel_path(mesh_factory, n_daemons):
     n = 32 * 150

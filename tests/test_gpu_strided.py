@@ -78,6 +78,35 @@ def test_seventy_op_list(mesh_factory, n_daemons, async_):
         a.free()
 
 
+@pytest.mark.parametrize("n_ops", [24, 25])  # the most ops the kernel arguments hold, and one more
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_list_at_the_inline_capacity(mesh_factory, n_daemons, n_ops):
+    # op i owns local [i * slot, +slot) and remote [i * rslot, +rslot): 1 to 3 rows of 16 to 5000 bytes,
+    # odd paddings and offsets; ops of no bytes first, last and two in a row; every third op a get
+    slot, rslot = 3 * 5008 + 64, 3 * 5016 + 64
+    sizes = (16, 5000, 17, 4096, 255, 4097, 1024, 33)
+    ops = []
+    for i in range(n_ops):
+        rb = 0 if i in (0, 7, 8, n_ops - 1) else sizes[i % len(sizes)]
+        ops.append([i % 3 != 1, i * slot + i % 16, i * rslot + (5 * i) % 32, rb, 1 + i % 3, rb + (0, 1, 5)[i % 3],
+                    rb + (0, 3, 16)[(i // 3) % 3]])
+    ops[8][4] = 0  # an op without rows as well
+    ops = np.asarray(ops, dtype=np.int64)
+    local_bytes, remote_bytes = n_ops * slot, (n_ops * rslot + UNIT - 1) // UNIT * UNIT
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, local_bytes, remote_bytes, n_daemons)
+        local, remote = fill_pair(a, local_bytes, remote_bytes, seed=n_ops, random_remote=True)
+        before = api.counters()
+        a.strided_batch(ops)
+        after = api.counters()
+        assert after["n_strided_ops"] == before["n_strided_ops"] + n_ops
+        assert after["bytes_strided"] == before["bytes_strided"] + moved_bytes(ops)
+        want_l, want_r = model(local, remote, ops)
+        assert np.array_equal(read_local(a, 0, local_bytes).numpy(), want_l)
+        assert np.array_equal(remote_bytes_of(a, local_bytes, remote_bytes), want_r)
+        a.free()
+
+
 @pytest.mark.parametrize("n_daemons", N_DAEMONS)
 def test_same_bytes_as_a_batch_of_rows(mesh_factory, n_daemons):
     ops, local_bytes, remote_bytes = mixed_list(30, seed=5)  # 30 strided ops: more than the inline count too
