@@ -59,7 +59,7 @@ static int acc_impl(ocm_alloc_t a, const struct ocm_acc_params *ops, int n_ops, 
     std::vector<XferBatchOp> v((size_t)n_ops, XferBatchOp{});
     for (int i = 0; i < n_ops; i++) acc_pack(ops[i], &v[i]);
     XferBatchArgs args;
-    list_fill_args(a, v, kAccTileShift, [](XferBatchOp *o, uint32_t n, uint32_t) { return acc_plan(o, n); }, &args);
+    if (list_fill_args(a, v, kAccTileShift, [](XferBatchOp *o, uint32_t n, uint32_t) { return acc_plan(o, n); }, &args) != 0) return -1;
     return run_list(a, args, v, xfer_acc_launch, (flags & OCM_BATCH_ASYNC) != 0);
 }
 

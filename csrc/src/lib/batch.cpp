@@ -69,7 +69,7 @@ int list_staging(lib_alloc *a, size_t need, hipStream_t st) {
 int batch_put_abs(lib_alloc *dst, std::vector<XferBatchOp> &v) {
     if (v.empty()) return 0;
     XferBatchArgs args;
-    list_fill_args(dst, v, 0, xfer_batch_plan, &args);
+    if (list_fill_args(dst, v, 0, xfer_batch_plan, &args) != 0) return -1;
     args.lin = nullptr;
     args.abs_lin = 1;
     if (args.total_tiles == 0) return 0;
@@ -98,7 +98,7 @@ static int batch_impl(ocm_alloc_t a, const struct ocm_params *ops, int n_ops, in
     DeviceGuard guard(s.device);
     std::vector<XferBatchOp> v = batch_descriptors(ops, n_ops);
     XferBatchArgs args;
-    list_fill_args(a, v, 0, xfer_batch_plan, &args);
+    if (list_fill_args(a, v, 0, xfer_batch_plan, &args) != 0) return -1;
     if (args.total_tiles == 0) return 0;  // only empty ops
     return run_list(a, args, v, xfer_batch_launch, async, &s.ctr.n_batch_launches);
 }
@@ -180,7 +180,7 @@ int ocm_plan_add(ocm_plan_t p, ocm_alloc_t a, const struct ocm_params *ops, int 
     ocm_plan::Stage st;
     st.a = a;
     std::vector<XferBatchOp> v = batch_descriptors(ops, n_ops);
-    list_fill_args(a, v, 0, xfer_batch_plan, &st.args);
+    if (list_fill_args(a, v, 0, xfer_batch_plan, &st.args) != 0) return -1;
     if (st.args.total_tiles == 0) return 0;
     if (n_ops > kXferInlineOps) {
         const size_t need = list_upload_bytes<XferBatchOp>(v.size(), st.args.grid);

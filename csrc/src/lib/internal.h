@@ -1,7 +1,8 @@
 // libocm internals shared by the library's translation units (not installed).
 //
 // runtime.cpp  process state, mailbox RPC, IPC/memfd import cache, local halves
-// transfer.cpp copy engine: segments, lanes/events, copy service, xfer, local copies
+// transfer.cpp copy engine: segments, lanes/events, xfer and its engines, local copies
+// service.cpp  the resident copy service's host side: lanes, start/park/stop, armer, service_xfer
 // net.cpp      network-tier client (owners on other nodes)
 // batch.cpp    batched one-sided ops, stream interop, transfer plans (hipGraph)
 // quant.cpp    converting one-sided ops (ocm_copy_onesided_quant: MXFP8 records)
@@ -466,6 +467,32 @@ inline int log2_exact(uint64_t v) {
     return __builtin_ctzll(v);
 }
 
+// The pair's side of a kernel's launch arguments (any of the argument structs with
+// ext, n_ext and unit_shift): the extent table, its length and, for a striped pair,
+// log2 of the stripe unit. Returns that shift (0: not striped), or -1 when the pair is
+// striped and its unit is not a power of two or is below 2^min_shift (4 for the
+// kernels that need 16-byte units); unit_shift is then left alone.
+template <class Args>
+int pair_side_shift(uint64_t unit, int min_shift, Args *args) {
+    const int sh = args->n_ext > 1 ? log2_exact(unit) : 0;
+    if (sh < 0 || (args->n_ext > 1 && sh < min_shift)) return -1;
+    args->unit_shift = (uint32_t)sh;
+    return sh;
+}
+template <class Args>
+int pair_side(const lib_alloc *a, int min_shift, Args *args) {
+    for (size_t i = 0; i < a->ext.size(); i++) args->ext[i] = a->ext[i].dptr;
+    args->n_ext = (uint32_t)a->ext.size();
+    return pair_side_shift(a->stripe_unit, min_shift, args);
+}
+// The same over raw extent pointers (ocm_x_xfer, ocm_x_batch).
+template <class Args>
+int pair_side(void *const *ext, int n_ext, uint64_t unit, int min_shift, Args *args) {
+    for (int i = 0; i < n_ext; i++) args->ext[i] = static_cast<char *>(ext[i]);
+    args->n_ext = (uint32_t)n_ext;
+    return pair_side_shift(unit, min_shift, args);
+}
+
 // ---- import cache (runtime.cpp)
 int import_extent(Extent &e);
 int slab_fd_from_owner(int owner, uint32_t slab_id, uint32_t tier);
@@ -517,25 +544,14 @@ int honor_dep(lib_alloc *a, hipStream_t st, bool host_wait);
 int wait_alloc(lib_alloc *a);
 hipStream_t lane_stream(lib_alloc *a);
 int sync_stream();
-int service_start(unsigned long long first_seq, const XferArgs *inline_x = nullptr, bool strict = false);
-void service_park();
-void service_stop();
+// The end of an async op queued on `st` (lane_stream): records the allocation's event
+// on its lane, or, with no lane available, completes the op now.
+int async_done(lib_alloc *a, hipStream_t st);
 // The hang watch's dump of library state (OCM_HANG_DUMP_S; runtime.cpp).
 void print_hang_state(int fd);
 // Close an HBM mapping of another process's slab: its per-device views, then the import
 // itself (a DMA-BUF import or an IPC open). runtime.cpp.
 void close_gpu_mapping(Mapping &m);
-// OCM_SERVICE_EAGER: the copy service's setup at ocm_init (transfer.cpp)
-int service_prepare();
-// OCM_SERVICE_PREARM: the idle-time armer thread (transfer.cpp)
-void service_armer_start();
-void service_armer_note_op(uint64_t t_done);
-// strict: an extent is in another GPU's HBM (kServiceGangStrict).
-// 0: done; -1: failed, and no instance holds the request any more (a launch may
-// redo the op); -2: failed and the instance could not be drained (no fallback).
-int service_xfer(XferArgs x, unsigned solo_tiles, bool hbm, bool strict);
-// Before a library launch: park the service when it may share the launch's hardware queue.
-void before_launch();
 // `done` (optional, async launches on a lane): receives the kernel-published
 // completion flag of the launch, or flag == nullptr when the op has none.
 int xfer(lib_alloc *a, bool put, char *lin, Loc lloc, uint64_t rem_off, uint64_t len, bool async,
@@ -549,6 +565,22 @@ int push_get(lib_alloc *a, char *lin, uint64_t rem_off, uint64_t len, hipStream_
 void push_release();
 // An address of extent e valid on device `dev` (its owner's GPU), opening its slab there once.
 char *extent_view(const Extent &e, int dev);
+
+// ---- copy service (service.cpp)
+// OCM_SERVICE_EAGER: the copy service's setup at ocm_init
+int service_prepare();
+int service_start(unsigned long long first_seq, const XferArgs *inline_x = nullptr, bool strict = false);
+void service_park();
+void service_stop();
+// OCM_SERVICE_PREARM: the idle-time armer thread
+void service_armer_start();
+void service_armer_note_op(uint64_t t_done);
+// strict: an extent is in another GPU's HBM (kServiceGangStrict).
+// 0: done; -1: failed, and no instance holds the request any more (a launch may
+// redo the op); -2: failed and the instance could not be drained (no fallback).
+int service_xfer(XferArgs x, unsigned solo_tiles, bool hbm, bool strict);
+// Before a library launch: park the service when it may share the launch's hardware queue.
+void before_launch();
 
 // ---- descriptor lists (batches and their kin): lists.h
 

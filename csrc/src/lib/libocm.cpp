@@ -163,7 +163,7 @@ int ocm_init(void) {
     s.svc_drain_ns = 1000000ull * (unsigned long long)std::max(1, env_int("OCM_SERVICE_DRAIN_MS", 10000));
     s.svc_box_reset_always = env_int("OCM_SERVICE_BOX_RESET", 0) != 0;
     s.svc_lanes_max = (unsigned)std::max(1, std::min(env_int("OCM_SERVICE_STREAMS", 4), 16));
-    // armed only while idle, and for at most OCM_SERVICE_PREARM_MS (transfer.cpp armer); off by
+    // armed only while idle, and for at most OCM_SERVICE_PREARM_MS (service.cpp armer); off by
     // default since round 6: an armed instance slows every other queue's dispatches (internal.h)
     s.svc_prearm = env_int("OCM_SERVICE_PREARM", 0) != 0;
     s.svc_inline = env_int("OCM_SERVICE_INLINE", 1) != 0;
@@ -872,13 +872,7 @@ int ocm_x_adam_multi(ocm_alloc_t a, int count, void *const *p, const void *const
     auto fits = [rb](uint64_t off, uint64_t len) { return off <= rb && len <= rb - off; };
     AdamMultiArgs x;
     std::memset(&x, 0, sizeof(x));
-    for (size_t i = 0; i < a->ext.size(); i++) x.c.ext[i] = a->ext[i].dptr;
-    x.c.n_ext = (uint32_t)a->ext.size();
-    if (x.c.n_ext > 1) {
-        const int sh = log2_exact(a->stripe_unit);
-        if (sh < 4) OCM_FAIL(-1, "ocm_x_adam_multi: stripe unit unusable");
-        x.c.unit_shift = (uint32_t)sh;
-    }
+    if (pair_side(a, 4, &x.c) < 0) OCM_FAIL(-1, "ocm_x_adam_multi: stripe unit unusable");
     x.c.b1 = hp[0];
     x.c.b2 = hp[1];
     x.c.eps = hp[2];
@@ -931,13 +925,8 @@ static int adam_common(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64
     x.g = static_cast<const float *>(g);
     x.bf16 = bf16 ? 1u : 0u;
     x.w_off = w_off;
-    for (size_t i = 0; i < a->ext.size(); i++) x.ext[i] = a->ext[i].dptr;
-    x.n_ext = (uint32_t)a->ext.size();
-    if (x.n_ext > 1) {
-        const int sh = log2_exact(a->stripe_unit);
-        if (sh < 4) OCM_FAIL(-1, "ocm_x_adam: stripe unit %llu unusable", (unsigned long long)a->stripe_unit);
-        x.unit_shift = (uint32_t)sh;
-    }
+    if (pair_side(a, 4, &x) < 0)
+        OCM_FAIL(-1, "ocm_x_adam: stripe unit %llu unusable", (unsigned long long)a->stripe_unit);
     x.m_off = m_off;
     x.v_off = v_off;
     x.n = n;
@@ -1302,16 +1291,10 @@ int ocm_x_xfer(int device, void *lin, void **ext, int n_ext, uint64_t unit, uint
     XferArgs x;
     std::memset(&x, 0, sizeof(x));
     x.lin = static_cast<char *>(lin);
-    for (int i = 0; i < n_ext; i++) x.ext[i] = static_cast<char *>(ext[i]);
-    x.n_ext = (uint32_t)n_ext;
     x.rem_off = rem_off;
     x.len = len;
     x.put = (uint32_t)put;
-    if (n_ext > 1) {
-        int sh = log2_exact(unit);
-        if (sh < 4) return -1;
-        x.unit_shift = (uint32_t)sh;
-    }
+    if (pair_side(ext, n_ext, unit, 4, &x) < 0) return -1;
     XferTuning t = xfer_tuning_from_env();
     if (variant) t.variant = variant;
     if (blocks) t.max_blocks = blocks;
@@ -1336,13 +1319,7 @@ int ocm_x_batch(int device, void *lin, void **ext, int n_ext, uint64_t unit, con
     XferBatchArgs args;
     std::memset(&args, 0, sizeof(args));
     args.lin = static_cast<char *>(lin);
-    for (int i = 0; i < n_ext; i++) args.ext[i] = static_cast<char *>(ext[i]);
-    args.n_ext = (uint32_t)n_ext;
-    if (n_ext > 1) {
-        const int sh = log2_exact(unit);
-        if (sh < 4) return -1;
-        args.unit_shift = (uint32_t)sh;
-    }
+    if (pair_side(ext, n_ext, unit, 4, &args) < 0) return -1;
     args.tile_shift = xfer_batch_tile_shift(args.n_ext, args.unit_shift);
     std::vector<XferBatchOp> v((size_t)n_ops);
     for (int i = 0; i < n_ops; i++) {

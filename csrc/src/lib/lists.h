@@ -74,17 +74,18 @@ void list_plan_args(Args *args, std::vector<Op> &v, Plan plan) {
 // Launch arguments of a list on `a`: the pair's side (the linear base, the extents and
 // how they stripe), then the plan's (list_plan_args). elem_shift: the tile shift of a
 // kind that cuts tiles in elements; 0: byte tiles, xfer_batch_tile_shift of the pair.
+// -1: the pair's stripe unit is unusable (the error is set).
 template <class Args, class Op, class Plan>
-void list_fill_args(lib_alloc *a, std::vector<Op> &v, uint32_t elem_shift, Plan plan, Args *args) {
+int list_fill_args(lib_alloc *a, std::vector<Op> &v, uint32_t elem_shift, Plan plan, Args *args) {
     std::memset(args, 0, sizeof(*args));
     args->lin = static_cast<char *>(a->local);
     static_assert(sizeof(args->ext) / sizeof(args->ext[0]) == kXferMaxExtents, "extent table of a pair");
-    for (size_t i = 0; i < a->ext.size(); i++) args->ext[i] = a->ext[i].dptr;
-    args->n_ext = (uint32_t)a->ext.size();
-    args->unit_shift = args->n_ext > 1 ? (uint32_t)log2_exact(a->stripe_unit) : 0;
+    if (pair_side(a, 0, args) < 0)
+        OCM_FAIL(-1, "stripe unit %llu is not a power of two", (unsigned long long)a->stripe_unit);
     args->host_tier = (!a->any_gpu && !a->any_net) ? 1u : 0u;
     args->tile_shift = elem_shift ? elem_shift : xfer_batch_tile_shift(args->n_ext, args->unit_shift);
     list_plan_args(args, v, plan);
+    return 0;
 }
 
 // A large list's upload: the descriptors, then the wave table.
@@ -133,13 +134,7 @@ int run_list(lib_alloc *a, Args &args, const std::vector<Op> &v,
     err = launch(args, s.tuning, st);
     if (err != hipSuccess) OCM_FAIL(-1, "batch launch failed: %s", hipGetErrorString(err));
     if (n_launches) (*n_launches)++;
-    if (async && st != s.stream && a->ev) {
-        err = hipEventRecord(a->ev, st);
-        if (err != hipSuccess) OCM_FAIL(-1, "event record failed: %s", hipGetErrorString(err));
-        a->async_pending = true;
-        return 0;
-    }
-    return sync_stream();
+    return async ? async_done(a, st) : sync_stream();
 }
 
 // Copy absolute device ranges (op.lin_off = address) into dst's remote half, one launch.

@@ -79,7 +79,7 @@ static int quant_impl(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_o
         v[i].pad = ops[i].dtype;
     }
     XferBatchArgs args;
-    list_fill_args(a, v, kQuantTileShift, [](XferBatchOp *o, uint32_t n, uint32_t) { return xfer_quant_plan(o, n); }, &args);
+    if (list_fill_args(a, v, kQuantTileShift, [](XferBatchOp *o, uint32_t n, uint32_t) { return xfer_quant_plan(o, n); }, &args) != 0) return -1;
     return run_list(a, args, v, xfer_quant_launch, (flags & OCM_BATCH_ASYNC) != 0);
 }
 

@@ -53,7 +53,7 @@ static int strided_impl(ocm_alloc_t a, const struct ocm_strided_params *ops, int
         v[i].put = ops[i].op_flag != 0;
     }
     XferStridedArgs args;
-    list_fill_args(a, v, 0, xfer_strided_plan, &args);
+    if (list_fill_args(a, v, 0, xfer_strided_plan, &args) != 0) return -1;
     return run_list(a, args, v, xfer_strided_launch, async);
 }
 

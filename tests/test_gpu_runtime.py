@@ -74,6 +74,77 @@ def test_striped_hbm_over_three_owners(mesh_factory):
         a.free()
 
 
+@pytest.mark.parametrize("engine", ["service", "launch", "async", "dma", "host"])
+def test_striped_unaligned_range_per_engine(mesh_factory, monkeypatch, engine):
+    """A pair striped over three extents at the smallest stripe unit the allocator
+    accepts (4 KiB); the range starts 16 bytes before a unit boundary and is
+    4 units + 48 bytes long: unaligned head and tail, every extent, and a wrap into
+    the second stripe row. Put a seeded pattern, get it back into a cleared local
+    half, compare every byte, and the 64 bytes around the range in both halves keep
+    their guard. Once per engine of xfer(): the copy service (blocking, default), a
+    kernel launch (service off, register kernel), the lane launch and the async tail
+    (async + wait), DMA pieces (variant 3), and a host-resident local half on a
+    host-tier pair, whose pieces this thread copies after the queued work."""
+    unit, guard = 4096, 64
+    n, loff, roff, size = 8 * unit, guard, unit - 16, 4 * unit + 48
+    if engine == "launch":
+        monkeypatch.setenv("OCM_SERVICE_MAX", "0")
+    m = mesh_factory(4, gpus=[0, 0, 0, 0], policy="stripe")
+    with api.Client(daemon_rank=0, gpu=0, ns=m.ns) as c:
+        if engine == "host":
+            a = c.alloc(api.OCM_REMOTE_RDMA, local_bytes=n, remote_bytes=n, flags=api.OCM_ALLOC_HOST_TIER,
+                        stripe_unit=unit)
+        else:
+            a = c.alloc(api.OCM_REMOTE_GPU, local_bytes=n, remote_bytes=n, stripe_unit=unit)
+        info = a.remote_info()
+        want_tier = api.OCM_TIER_HOST if engine == "host" else api.OCM_TIER_GPU
+        assert len(info["extents"]) == 3 and all(e["tier"] == want_tier for e in info["extents"]), info
+        loc = a.local_tensor()
+        assert loc.device.type == ("cpu" if engine == "host" else "cuda")
+        gen = torch.Generator().manual_seed(4096)
+        pattern = torch.randint(0, 256, (size,), dtype=torch.uint8, generator=gen).to(loc.device)
+        remote_guard = (torch.arange(n, dtype=torch.int64) * 7 + 3).to(torch.uint8).to(loc.device)
+        local_guard = (torch.arange(n, dtype=torch.int64) * 5 + 1).to(torch.uint8).to(loc.device)
+
+        def sync():
+            if loc.device.type == "cuda":
+                torch.cuda.synchronize()
+
+        async_ = engine == "async"
+        try:
+            loc.copy_(remote_guard)
+            sync()
+            a.put(0, 0, n)  # the remote half holds its guard everywhere
+            ops0 = api.service_stats()["ops"]
+            if engine == "launch":
+                api.set_tuning(variant=1)
+            elif engine == "dma":
+                api.set_tuning(variant=3)
+            loc[loff:loff + size] = pattern
+            sync()
+            a.put(loff, roff, size, async_=async_)
+            if async_:
+                a.wait()
+            loc.copy_(local_guard)  # cleared: nothing of the pattern is left in the local half
+            sync()
+            a.get(loff, roff, size, async_=async_)
+            if async_:
+                a.wait()
+            served = api.service_stats()["ops"] - ops0
+            assert served == 2 if engine == "service" else served == 0, (engine, served)
+            assert torch.equal(loc[loff:loff + size], pattern), engine
+            after = slice(loff + size, loff + size + guard)
+            assert torch.equal(loc[:loff], local_guard[:loff]) and torch.equal(loc[after], local_guard[after]), engine
+            api.set_tuning()
+            a.get(0, 0, n)  # the whole remote half, by the default engine
+            assert torch.equal(loc[roff:roff + size], pattern), engine
+            for g in (slice(roff - guard, roff), slice(roff + size, roff + size + guard)):
+                assert torch.equal(loc[g], remote_guard[g]), (engine, g)
+        finally:
+            api.set_tuning()
+            a.free()
+
+
 def test_host_tier_pair_and_copy_in_out(mesh_factory):
     m = mesh_factory(1, gpus=[0])
     with api.Client(daemon_rank=0, gpu=0, ns=m.ns) as c:

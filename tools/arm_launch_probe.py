@@ -1,7 +1,7 @@
 """What an idle pre-armed copy-service instance costs OTHER work's launch latency
 (round 6). While the copy service is idle, libocm keeps its next
 instance queued behind a closed barrier-AND gate on its own AQL queue
-(OCM_SERVICE_PREARM, transfer.cpp's armer). The packet processor holds that packet at
+(OCM_SERVICE_PREARM, service.cpp's armer). The packet processor holds that packet at
 the queue's head until the gate opens. Does the blocked queue slow the dispatch of
 kernels on other queues, say a small torch kernel or the control plane's tick kernels?
 
