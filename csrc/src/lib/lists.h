@@ -47,17 +47,13 @@ int list_enter(const ListNames &k, std::unique_lock<std::recursive_mutex> &lk, l
     return PATH_HOST;
 }
 
-// The ABI side of every list call: trace range, timing, the kind's counters after a
-// success (count(counters, ns)) and the op log, which records `traced` bytes.
+// The ABI side of every list call (abi_call, unwatched): the kind's counters move after a
+// success (count(counters, ns)), and the op log records `traced` bytes.
 template <class Impl, class Count>
 int list_call(const ListNames &k, const uint64_t &traced, Impl impl, Count count) {
-    TraceRange tr(k.range);
-    const uint64_t t0 = now_ns();
-    const int rc = impl();
-    const uint64_t t1 = now_ns();
-    if (rc == 0) count(S().ctr, t1 - t0);
-    trace_op(k.op, traced, t0, t1, rc);
-    return rc;
+    return abi_call(k.range, false, k.op, traced, impl, [&](OpCounters &c, uint64_t ns, bool ok) {
+        if (ok) count(c, ns);
+    });
 }
 
 // The plan's side of launch arguments whose pair's side is set: the descriptors `v`

@@ -112,8 +112,8 @@ int net_piece(const Extent &e, bool put, char *lin, Loc lloc, uint64_t ext_off, 
     const bool dev = lloc == LOC_DEVICE;
     // Parts: one per stream, each at least net_split_min bytes, 64 KiB aligned.
     int k = 1;
-    if (s.net_streams > 1 && len >= 2 * s.net_split_min)
-        k = (int)std::min<uint64_t>((uint64_t)s.net_streams, len / s.net_split_min);
+    if (s.cfg.net_streams > 1 && len >= 2 * s.cfg.net_split_min)
+        k = (int)std::min<uint64_t>((uint64_t)s.cfg.net_streams, len / s.cfg.net_split_min);
     std::vector<NetConn *> conns((size_t)k);
     for (int i = 0; i < k; i++) {
         conns[(size_t)i] = net_conn(e.ep, e.net_token, i);

@@ -29,12 +29,6 @@ void print_hang_state(int fd) {
     }
 }
 
-int env_int(const char *k, int dflt) {
-    const char *v = std::getenv(k);
-    return (v && *v) ? std::atoi(v) : dflt;
-}
-
-
 long now_ms() {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -120,7 +114,7 @@ int rpc(Msg &req, Msg *reply, int timeout_ms) {
     // A reply usually lands within a few microseconds: poll for it (bounded,
     // OCM_RPC_SPIN_US) before sleeping, which adds a wake-up.
     const long deadline = now_ms() + timeout_ms;
-    uint64_t spin = s.rpc_spin_ns;
+    uint64_t spin = s.cfg.rpc_spin_ns;
     for (;;) {
         const int rc = recv_record(reply, deadline, spin);
         spin = 0;
@@ -134,7 +128,7 @@ int rpc(Msg &req, Msg *reply, int timeout_ms) {
 int recv_seq(Msg *m, uint64_t seq, uint32_t type, int timeout_ms) {
     const long deadline = now_ms() + timeout_ms;
     for (;;) {
-        const int rc = recv_record(m, deadline, S().rpc_spin_ns);
+        const int rc = recv_record(m, deadline, S().cfg.rpc_spin_ns);
         if (rc < 0) return -1;
         if (rc == 0) OCM_FAIL(-1, "timed out waiting for %s", msg_type_str(type));
         if (m->seq == seq && m->type == type) return 0;
@@ -538,7 +532,7 @@ void PinnedArena::trim() {
     // Unpin idle chunks beyond the keep budget (largest first).
     uint64_t idle = 0;
     for (auto &kv : chunks_) idle += kv.second.ra.empty() ? kv.second.bytes : 0;
-    while (idle > s.pinned_keep) {
+    while (idle > s.cfg.pinned_keep) {
         auto victim = chunks_.end();
         for (auto it = chunks_.begin(); it != chunks_.end(); ++it)
             if (it->second.ra.empty() && (victim == chunks_.end() || it->second.bytes > victim->second.bytes)) victim = it;
@@ -567,7 +561,7 @@ int free_local_half(lib_alloc *a) {
         // keep it for an exact-size reuse, or return it to the pool, ordered after
         // every transfer queued on s.stream.
         const uint64_t kMaxCachedBlock = 256ull << 20;
-        if (a->local_bytes <= kMaxCachedBlock && s.dev_cache_bytes + a->local_bytes <= s.dev_cache_cap) {
+        if (a->local_bytes <= kMaxCachedBlock && s.dev_cache_bytes + a->local_bytes <= s.cfg.dev_cache_cap) {
             s.dev_cache.emplace(a->local_bytes, a->local);
             s.dev_cache_bytes += a->local_bytes;
         } else {

@@ -99,7 +99,7 @@ static int service_setup() {
                           hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
             (void)hipGetLastError();
             s.svc = nullptr;
-            s.svc_max = 0;
+            s.cfg.svc_max = 0;
             OCM_FAIL(-1, "copy service: no coherent host memory");
         }
         std::memset(s.svc, 0, sizeof(ServiceSlot));
@@ -108,7 +108,7 @@ static int service_setup() {
         // device; otherwise HIP streams (and no lone lead: a device-wide synchronize
         // would wait for it).
         s.svc_aql = false;
-        if (s.svc_queue_aql) {
+        if (s.cfg.svc_queue_aql) {
             const char *why = nullptr;
             if (aql_open(s.device, &why) != 0)
                 OCM_INFO("copy service on HIP streams: AQL queue unavailable (%s)", why ? why : "?");
@@ -122,7 +122,7 @@ static int service_setup() {
                               aql_kernel(kServiceBoxClearSymbol, &s.svc_clear_kernel) != 0))
                 s.svc_clear_kernel = AqlKernel{};
         }
-        if (!s.svc_aql) s.svc_lone_ticks = 0;
+        if (!s.svc_aql) s.cfg.svc_lone_ticks = 0;
         // Streams of their own priority: HIP shares its few hardware queues
         // (GPU_MAX_HW_QUEUES) among a process's streams, and a launch on a stream
         // that shares the service's queue waits behind the persistent kernel until
@@ -137,7 +137,7 @@ static int service_setup() {
         if (service_new_lane() < 0 && s.svc_aql) {
             OCM_INFO("copy service on HIP streams: no AQL queue could be created");
             s.svc_aql = false;
-            s.svc_lone_ticks = 0;
+            s.cfg.svc_lone_ticks = 0;
             service_new_lane();
         }
         if (s.svc_lanes.empty() && s.svc_prio_ok) {
@@ -146,12 +146,12 @@ static int service_setup() {
             service_new_lane();
         }
         if (s.svc_lanes.empty()) {
-            s.svc_max = 0;
+            s.cfg.svc_max = 0;
             OCM_FAIL(-1, "copy service: no stream or device mailbox");
         }
         s.svc_lane = 0;
-        const bool gangrec = (s.svc_proto & kServiceProtoGangRec) && s.svc_blocks > 1;
-        const bool wc = (s.svc_proto & kServiceProtoWCReq) != 0;
+        const bool gangrec = (s.cfg.svc_proto & kServiceProtoGangRec) && s.cfg.svc_blocks > 1;
+        const bool wc = (s.cfg.svc_proto & kServiceProtoWCReq) != 0;
         if (gangrec || wc) {
             // page 0: the small-op record when write-combined; page 1: the gang record
             const unsigned flags = (wc ? hipHostMallocWriteCombined : hipHostMallocCoherent) | hipHostMallocMapped;
@@ -166,8 +166,8 @@ static int service_setup() {
                 if (wc) s.svc_req = reinterpret_cast<ServiceReq *>(s.svc_rec_pages);
                 if (gangrec) {
                     s.svc_greq = reinterpret_cast<ServiceReq *>(s.svc_rec_pages + 4096);
-                    s.svc_greq_copies = (s.svc_proto & kServiceProtoCopies)
-                                            ? std::max(1u, std::min(std::min(s.svc_direct, s.svc_blocks),
+                    s.svc_greq_copies = (s.cfg.svc_proto & kServiceProtoCopies)
+                                            ? std::max(1u, std::min(std::min(s.cfg.svc_direct, s.cfg.svc_blocks),
                                                                     (unsigned)kServiceGangCopiesMax))
                                             : 1u;
                 }
@@ -193,7 +193,7 @@ int service_prepare() {
         l.checkins = 0;
     }
     (void)hipGetLastError();
-    if (l.aql && s.svc_prearm) {
+    if (l.aql && s.cfg.svc_prearm) {
         service_armer_start();
         service_armer_note_op(now_ns());  // arms once the idle period has passed
     }
@@ -223,9 +223,9 @@ int service_start(unsigned long long first_seq, const XferArgs *inline_x, bool s
     int pick = -1;
     bool overlap = false;
     const int n = (int)s.svc_lanes.size();
-    const bool whole = s.svc_lane >= 0 && svc_word(&s.svc->roster) >= s.svc_blocks;
-    if (whole && !s.svc_aql && !s.svc_relaunch_query) pick = s.svc_lane;
-    if (whole && s.svc_aql && !s.svc_lanes[(size_t)s.svc_lane].dirty && !s.svc_box_reset_always &&
+    const bool whole = s.svc_lane >= 0 && svc_word(&s.svc->roster) >= s.cfg.svc_blocks;
+    if (whole && !s.svc_aql && !s.cfg.svc_relaunch_query) pick = s.svc_lane;
+    if (whole && s.svc_aql && !s.svc_lanes[(size_t)s.svc_lane].dirty && !s.cfg.svc_box_reset_always &&
         s.svc_lanes[(size_t)s.svc_lane].gang_total <= (1ull << 30)) {  // a box clear would make a third dispatch
         const long run = aql_lane_inflight(&s.svc_lanes[(size_t)s.svc_lane].q);
         if (run <= 1) {
@@ -237,7 +237,7 @@ int service_start(unsigned long long first_seq, const XferArgs *inline_x, bool s
         const int i = (s.svc_lane + k) % n;
         if (lane_idle(s.svc_lanes[(size_t)i])) pick = i;
     }
-    if (pick < 0 && (unsigned)n < s.svc_lanes_max) pick = service_new_lane();
+    if (pick < 0 && (unsigned)n < s.cfg.svc_lanes_max) pick = service_new_lane();
     if (pick < 0) {
         pick = s.svc_lane;
         if (s.svc_lanes[(size_t)pick].aql) {
@@ -246,9 +246,9 @@ int service_start(unsigned long long first_seq, const XferArgs *inline_x, bool s
                              __ATOMIC_RELEASE);
             __builtin_ia32_sfence();
         }
-        if (lane_drain(s.svc_lanes[(size_t)pick], s.svc_drain_ns, kDrainStart) != 0) {
+        if (lane_drain(s.svc_lanes[(size_t)pick], s.cfg.svc_drain_ns, kDrainStart) != 0) {
             s.svc_wedged = true;
-            s.svc_max = 0;
+            s.cfg.svc_max = 0;
             OCM_FAIL(-1, "copy service: no lane drained within OCM_SERVICE_DRAIN_MS");
         }
     }
@@ -268,7 +268,7 @@ int service_start(unsigned long long first_seq, const XferArgs *inline_x, bool s
     service_store_seq(s.svc_req, 0ull);  // clear a STOP left by a parked instance
     if (s.svc_greq) service_store_seq(s.svc_greq, 0ull, s.svc_greq_copies);
     // the gang counter mirror stays below the 31-bit target field (ocm/xfer.h)
-    const bool reset = l.dirty || s.svc_box_reset_always || l.gang_total > (1ull << 30);
+    const bool reset = l.dirty || s.cfg.svc_box_reset_always || l.gang_total > (1ull << 30);
     if (reset) {
         l.gang_total = 0;  // the launch zeroes the device counters
         l.checkins = 0;
@@ -280,15 +280,15 @@ int service_start(unsigned long long first_seq, const XferArgs *inline_x, bool s
     ka.slot = s.svc;
     ka.box = l.box;
     ka.first_seq = first_seq;
-    ka.idle_ticks = s.svc_idle_ticks;
-    ka.proto = s.svc_proto;
-    ka.direct_wgs = std::min(s.svc_direct, s.svc_blocks);
+    ka.idle_ticks = s.cfg.svc_idle_ticks;
+    ka.proto = s.cfg.svc_proto;
+    ka.direct_wgs = std::min(s.cfg.svc_direct, s.cfg.svc_blocks);
     ka.checkin_base = l.checkins;
     ka.epoch = s.svc_epoch;
-    ka.blocks = s.svc_blocks;
-    ka.degraded_idle_ticks = s.svc_degraded_idle_ticks;
-    ka.lone_ticks = l.aql ? s.svc_lone_ticks : 0;
-    if (inline_x && s.svc_inline) {
+    ka.blocks = s.cfg.svc_blocks;
+    ka.degraded_idle_ticks = s.cfg.svc_degraded_idle_ticks;
+    ka.lone_ticks = l.aql ? s.cfg.svc_lone_ticks : 0;
+    if (inline_x && s.cfg.svc_inline) {
         // the solo request the caller posts next, as it will post it (active 1, no target)
         const unsigned long long gang = 1ull | ((unsigned long long)s.svc_epoch << kServiceGangEpochShift) |
                                         (strict ? kServiceGangStrict : 0ull);
@@ -297,9 +297,9 @@ int service_start(unsigned long long first_seq, const XferArgs *inline_x, bool s
     }
     const uint64_t tl = now_ns();
     s.svc_ns_pick += tl - tq;
-    if (l.aql && s.svc_prearm && !s.svc_armer) service_armer_start();
+    if (l.aql && s.cfg.svc_prearm && !s.svc_armer) service_armer_start();
     s.svc_start_fired = false;
-    if (l.aql && s.svc_prearm && l.q.armed && !reset && aql_fire(&l.q, &ka, sizeof(ka)) == 0) {
+    if (l.aql && s.cfg.svc_prearm && l.q.armed && !reset && aql_fire(&l.q, &ka, sizeof(ka)) == 0) {
         // the instance the armer queued while the service was idle: write its arguments,
         // open its gate (the armer queues the next one once the service is idle again)
         s.svc_fires++;
@@ -312,30 +312,30 @@ int service_start(unsigned long long first_seq, const XferArgs *inline_x, bool s
         if (reset && s.svc_clear_kernel.object && !overlap) {
             ServiceBox *bx = l.box;
             if (aql_dispatch(&l.q, s.svc_clear_kernel, &bx, sizeof(bx), 1, 256) != 0) {
-                s.svc_max = 0;
+                s.cfg.svc_max = 0;
                 OCM_FAIL(-1, "copy service: gang box clear dispatch failed");
             }
             barrier = overlap = true;
         } else if (reset && (hipMemsetAsync(l.box, 0, sizeof(ServiceBox), s.stream) != hipSuccess ||
                              hipStreamSynchronize(s.stream) != hipSuccess)) {
             (void)hipGetLastError();
-            s.svc_max = 0;
+            s.cfg.svc_max = 0;
             OCM_FAIL(-1, "copy service: clearing the gang box failed");
         }
-        if (aql_dispatch(&l.q, s.svc_kernel, &ka, sizeof(ka), s.svc_blocks, 256, overlap, barrier) != 0) {
-            s.svc_max = 0;
+        if (aql_dispatch(&l.q, s.svc_kernel, &ka, sizeof(ka), s.cfg.svc_blocks, 256, overlap, barrier) != 0) {
+            s.cfg.svc_max = 0;
             OCM_FAIL(-1, "copy service dispatch failed");
         }
         if (overlap && !barrier) s.svc_overlaps++;
-    } else if (service_launch(ka, s.svc_blocks, reset, l.stream) != hipSuccess) {
+    } else if (service_launch(ka, s.cfg.svc_blocks, reset, l.stream) != hipSuccess) {
         (void)hipGetLastError();
-        s.svc_max = 0;
+        s.cfg.svc_max = 0;
         OCM_FAIL(-1, "copy service launch failed");
     }
     s.svc_ns_launch += now_ns() - tl;
     s.svc_epoch_starts++;
     l.dirty = false;
-    l.checkins += s.svc_blocks;  // every workgroup takes one ticket before the instance drains
+    l.checkins += s.cfg.svc_blocks;  // every workgroup takes one ticket before the instance drains
     s.svc_running = true;
     s.svc_launch_ns = now_ns();
     return 0;
@@ -359,9 +359,9 @@ void service_park() {
     service_post_stop();
     State::SvcLane &l = s.svc_lanes[(size_t)s.svc_lane];
     if (l.aql) {
-        if (lane_drain(l, s.svc_drain_ns, kDrainPark) != 0) {
+        if (lane_drain(l, s.cfg.svc_drain_ns, kDrainPark) != 0) {
             s.svc_wedged = true;
-            s.svc_max = 0;
+            s.cfg.svc_max = 0;
             OCM_WARN("copy service did not leave on STOP within OCM_SERVICE_DRAIN_MS; the service is off");
         }
     } else {
@@ -379,13 +379,13 @@ static void service_armer_try_arm() {
     State &s = S();
     std::unique_lock<std::recursive_mutex> lk(s.mu, std::try_to_lock);
     if (!lk.owns_lock() || s.svc_armer_stop.load()) return;
-    if (!s.svc || !s.svc_prearm || s.svc_lane < 0) return;
+    if (!s.svc || !s.cfg.svc_prearm || s.svc_lane < 0) return;
     State::SvcLane &l = s.svc_lanes[(size_t)s.svc_lane];
     if (!l.aql || l.q.armed || l.dirty) return;
     if (s.svc_running && svc_word(&s.svc->exited) == 0) return;  // an instance (a lone lead) still runs
     if (aql_lane_inflight(&l.q) != 0) return;
     DeviceGuard g(s.device);
-    if (aql_arm(&l.q, s.svc_kernel, sizeof(ServiceKernelArgs), s.svc_blocks, 256) == 0) s.svc_arms++;
+    if (aql_arm(&l.q, s.svc_kernel, sizeof(ServiceKernelArgs), s.cfg.svc_blocks, 256) == 0) s.svc_arms++;
 }
 
 // The window's end (OCM_SERVICE_PREARM_MS): cancel the instance still armed, so the
@@ -467,7 +467,7 @@ static void service_armer_loop() {
 void service_armer_start() {
     State &s = S();
     if (s.svc_armer) return;
-    s.svc_arm_after_ns = s.svc_idle_ticks * 10ull + (s.svc_lone_ticks * 10ull) + 500000ull;  // ticks: 100 MHz
+    s.svc_arm_after_ns = s.cfg.svc_idle_ticks * 10ull + (s.cfg.svc_lone_ticks * 10ull) + 500000ull;  // ticks: 100 MHz
     s.svc_armer_stop.store(false);
     s.svc_armer_pid = getpid();
     s.svc_armer = new std::thread(service_armer_loop);
@@ -512,7 +512,7 @@ void service_stop() {
     s.svc_running = false;
     for (State::SvcLane &l : s.svc_lanes) {  // every lane drained before its box goes
         if (l.aql) {
-            if (lane_drain(l, s.svc_drain_ns, kDrainStop) != 0) {
+            if (lane_drain(l, s.cfg.svc_drain_ns, kDrainStop) != 0) {
                 // never free what a kernel that did not leave may still touch
                 OCM_WARN("copy service: a lane did not drain at shutdown; its queue and box are leaked");
                 continue;
@@ -542,7 +542,7 @@ void service_stop() {
 static unsigned service_roster(unsigned want) {
     State &s = S();
     unsigned long long r = svc_word(&s.svc->roster);
-    while (r < want && now_ns() - s.svc_launch_ns < s.svc_roster_wait_ns) {
+    while (r < want && now_ns() - s.svc_launch_ns < s.cfg.svc_roster_wait_ns) {
         __builtin_ia32_pause();
         r = svc_word(&s.svc->roster);
     }
@@ -565,9 +565,9 @@ static int service_abort(unsigned long long seq, unsigned long long active, cons
     const unsigned long long roster = svc_word(&s.svc->roster);
     service_post_stop();
     s.svc_aborts++;
-    if (lane_drain(s.svc_lanes[(size_t)s.svc_lane], s.svc_drain_ns, kDrainAbort) != 0) {
+    if (lane_drain(s.svc_lanes[(size_t)s.svc_lane], s.cfg.svc_drain_ns, kDrainAbort) != 0) {
         s.svc_wedged = true;
-        s.svc_max = 0;
+        s.cfg.svc_max = 0;
         OCM_FAIL(-2, "copy service %s (seq %llu, %llu members, %llu done words, roster %llu, exited %llu) "
                      "and did not leave on STOP: not redoing the op",
                  why, seq, active, wg_in, roster, ex);
@@ -606,9 +606,9 @@ struct SvcTimes {
 static int size_and_post(SvcOp &o) {
     State &s = S();
     const XferArgs &x = o.x;
-    unsigned width = o.direct ? std::min(s.svc_direct, s.svc_blocks)
-                              : (o.hbm ? s.svc_blocks : std::min(s.svc_gang_host, s.svc_blocks));
-    if (!o.hbm && !x.put && x.len >= s.svc_host_get_narrow_min) width = std::min(width, s.svc_host_get_width);
+    unsigned width = o.direct ? std::min(s.cfg.svc_direct, s.cfg.svc_blocks)
+                              : (o.hbm ? s.cfg.svc_blocks : std::min(s.cfg.svc_gang_host, s.cfg.svc_blocks));
+    if (!o.hbm && !x.put && x.len >= s.cfg.svc_host_get_narrow_min) width = std::min(width, s.cfg.svc_host_get_width);
     if (service_gang_size(x, width, o.solo_tiles) > 1) {
         // A lone lead takes no gang: a full instance replaces it (the lead leaves
         // on the new epoch by itself; it holds no request of ours).
@@ -619,7 +619,7 @@ static int size_and_post(SvcOp &o) {
         width = service_roster(width);
     }
     o.active = service_gang_size(x, width, o.solo_tiles);
-    o.wgdone = service_wg_done(s.svc_proto, o.active);
+    o.wgdone = service_wg_done(s.cfg.svc_proto, o.active);
     unsigned long long target = 0;
     if (o.active > 1 && !o.wgdone) {  // WGDONE gangs leave the counter alone
         if (s.svc_lanes[(size_t)s.svc_lane].gang_total + o.active > kServiceGangTargetMask) {
@@ -631,7 +631,7 @@ static int size_and_post(SvcOp &o) {
             if (service_start(o.seq) != 0) return -1;
             width = std::min(width, service_roster(width));
             o.active = service_gang_size(x, width, o.solo_tiles);
-            o.wgdone = service_wg_done(s.svc_proto, o.active);
+            o.wgdone = service_wg_done(s.cfg.svc_proto, o.active);
         }
         State::SvcLane &l = s.svc_lanes[(size_t)s.svc_lane];
         if (o.active > 1 && !o.wgdone) {
@@ -665,8 +665,8 @@ __attribute__((noinline)) static void account_done(const SvcOp &o, SvcTimes &t, 
     s.svc_ops++;
     s.svc_ns_post += t.posted - t.t0;
     s.svc_ns_wait += t_done - t.posted;
-    if (s.svc_prearm) service_armer_note_op(t_done);
-    if (s.svc_proto & kServiceProtoTrace) {
+    if (s.cfg.svc_prearm) service_armer_note_op(t_done);
+    if (s.cfg.svc_proto & kServiceProtoTrace) {
         if (s.svc_optrace.empty()) s.svc_optrace.resize(kServiceOpTrace);
         s.svc_optrace[o.seq & (kServiceOpTrace - 1)] = {o.seq, t.enter, t.posted, t_done, (uint64_t)s.svc_lane,
                                                         t.dispatched ? 1ull : 0ull, o.active};
@@ -698,7 +698,7 @@ static int service_repost(SvcOp &o, unsigned long long ex) {
     State &s = S();
     DeviceGuard g(s.device);
     if (!ex) service_post_stop();
-    if (lane_drain(s.svc_lanes[(size_t)s.svc_lane], s.svc_drain_ns, kDrainRepost) != 0)
+    if (lane_drain(s.svc_lanes[(size_t)s.svc_lane], s.cfg.svc_drain_ns, kDrainRepost) != 0)
         return service_abort(o.seq, o.active, "left part of a request behind and did not drain");
     s.svc_running = false;
     s.svc_relaunches++;
@@ -725,8 +725,8 @@ static int service_repost(SvcOp &o, unsigned long long ex) {
 int service_xfer(XferArgs x, unsigned solo_tiles, bool hbm, bool strict) {
     State &s = S();
     if (xfer_normalize(x) != hipSuccess) OCM_FAIL(-1, "invalid transfer");
-    if (!hbm && x.len >= s.svc_host_tile_min && x.len <= s.svc_host_tile_max) {
-        const unsigned sh = x.put ? s.svc_host_tile_shift_put : s.svc_host_tile_shift_get;
+    if (!hbm && x.len >= s.cfg.svc_host_tile_min && x.len <= s.cfg.svc_host_tile_max) {
+        const unsigned sh = x.put ? s.cfg.svc_host_tile_shift_put : s.cfg.svc_host_tile_shift_get;
         if (sh >= 12 && sh < x.tile_shift) x.tile_shift = sh;
     }
     SvcOp o{x, solo_tiles, hbm, strict, false, ++s.svc_seq, 1, false, s.svc_req, 0};
@@ -749,7 +749,7 @@ int service_xfer(XferArgs x, unsigned solo_tiles, bool hbm, bool strict) {
         t.dispatched = now_ns();
         if (relaunched) s.svc_ns_relaunch += t.dispatched - t.enter;
     }
-    o.direct = s.svc_greq && o.x.len <= (hbm ? s.svc_direct_max_hbm : s.svc_direct_max_host);
+    o.direct = s.svc_greq && o.x.len <= (hbm ? s.cfg.svc_direct_max_hbm : s.cfg.svc_direct_max_host);
     t.t0 = now_ns();
     if (size_and_post(o) != 0) return -1;
     t.posted = now_ns();
@@ -774,7 +774,7 @@ int service_xfer(XferArgs x, unsigned solo_tiles, bool hbm, bool strict) {
                 const int rc = service_repost(o, ex);
                 if (rc != kOpReposted) return rc;
             }
-            if (now_ns() - t.t0 > s.svc_timeout_ns) return service_abort(o.seq, o.active, "did not complete a transfer in time");
+            if (now_ns() - t.t0 > s.cfg.svc_timeout_ns) return service_abort(o.seq, o.active, "did not complete a transfer in time");
         }
     }
 }

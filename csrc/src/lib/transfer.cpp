@@ -36,7 +36,7 @@ void segments(const lib_alloc *a, uint64_t rem_off, uint64_t len, std::vector<Se
 int wait_event(hipEvent_t ev) {
     State &s = S();
     hipError_t e = hipSuccess;
-    if (s.sync_mode == 1) {
+    if (s.cfg.sync_mode == 1) {
         while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
         }
     } else {
@@ -73,7 +73,7 @@ hipStream_t lane_stream(lib_alloc *a) {
     if (a->lane < 0) {
         if (s.lanes.empty()) {
             DeviceGuard g(s.device);
-            for (int i = 0; i < std::max(1, s.n_lanes); i++) {
+            for (int i = 0; i < std::max(1, s.cfg.n_lanes); i++) {
                 hipStream_t st = nullptr;
                 if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
                     (void)hipGetLastError();
@@ -83,7 +83,7 @@ hipStream_t lane_stream(lib_alloc *a) {
             }
         }
         if (s.lanes.empty()) return s.stream;
-        if (!s.lane_flags && s.launch_flags) {
+        if (!s.lane_flags && s.cfg.launch_flags) {
             DeviceGuard g(s.device);
             const size_t nl = s.lanes.size();
             if (hipHostMalloc(reinterpret_cast<void **>(&s.lane_flags), nl * 128,
@@ -91,7 +91,7 @@ hipStream_t lane_stream(lib_alloc *a) {
                 hipMalloc(reinterpret_cast<void **>(&s.lane_cnt), nl * 128) != hipSuccess ||
                 hipMemset(s.lane_cnt, 0, nl * 128) != hipSuccess) {
                 (void)hipGetLastError();
-                s.launch_flags = false;  // events only
+                s.cfg.launch_flags = false;  // events only
             } else {
                 std::memset(s.lane_flags, 0, nl * 128);
                 s.lane_flag_seq.assign(nl, 0);
@@ -115,11 +115,11 @@ int sync_stream() {
     if (!s.stream) return 0;
     DeviceGuard g(s.device);
     hipError_t e = hipSuccess;
-    if (s.sync_mode == 0 || !s.done) {
+    if (s.cfg.sync_mode == 0 || !s.done) {
         e = hipStreamSynchronize(s.stream);
     } else {
         e = hipEventRecord(s.done, s.stream);
-        if (e == hipSuccess && s.sync_mode == 1) {
+        if (e == hipSuccess && s.cfg.sync_mode == 1) {
             // Spin: lowest completion latency for small one-sided ops.
             while ((e = hipEventQuery(s.done)) == hipErrorNotReady) {
             }
@@ -247,9 +247,9 @@ static int xfer_service(lib_alloc *a, bool put, char *lin, uint64_t rem_off, uin
     // Gets from the host tier are bound by PCIe read round trips: two tiles
     // already go faster on two workgroups (64 KiB: 7.7 vs 8.4 us); puts and
     // HBM owners keep small requests on workgroup 0 (profiles/svc_v4_r02.json).
-    const unsigned solo = (!put && !a->any_gpu) ? std::min(s.svc_solo_tiles, s.svc_solo_tiles_host_get)
-                                                : s.svc_solo_tiles;
-    return service_xfer(x, solo, a->any_gpu, a->any_peer || s.svc_force_strict);
+    const unsigned solo = (!put && !a->any_gpu) ? std::min(s.cfg.svc_solo_tiles, s.cfg.svc_solo_tiles_host_get)
+                                                : s.cfg.svc_solo_tiles;
+    return service_xfer(x, solo, a->any_gpu, a->any_peer || s.cfg.svc_force_strict);
 }
 
 // Push-based get (XFER_PUSH): kernels on the owners' GPUs store into the local half.
@@ -266,7 +266,7 @@ static int xfer_kernel(lib_alloc *a, bool put, char *lin, uint64_t rem_off, uint
     // No resident poller during a large copy over PCIe (its doorbell reads share
     // the link) or when asked (A/B); without a queue of its own the service
     // would also hold this launch until its idle exit.
-    if ((s.svc_park_kernel || !a->any_gpu) && len > s.svc_limit(a)) service_park();
+    if ((s.cfg.svc_park_kernel || !a->any_gpu) && len > s.cfg.svc_limit(a)) service_park();
     before_launch();
     XferArgs x;
     if (pair_args(a, put, lin, rem_off, len, &x) != 0) return -1;
@@ -280,7 +280,7 @@ static int xfer_kernel(lib_alloc *a, bool put, char *lin, uint64_t rem_off, uint
         t.variant = !a->any_gpu ? XFER_PCIE : (same_gpu && len <= (256ull << 20)) ? XFER_LDS : XFER_REG;
     }
     XferDone dn;
-    if (done && async && len <= s.launch_flag_max && s.launch_flags && s.lane_flags && st != s.stream &&
+    if (done && async && len <= s.cfg.launch_flag_max && s.cfg.launch_flags && s.lane_flags && st != s.stream &&
         a->lane >= 0 && a->ev) {
         dn.flag = s.lane_flags + (size_t)a->lane * 16;
         dn.cnt = s.lane_cnt + (size_t)a->lane * 32;
@@ -323,12 +323,12 @@ int xfer(lib_alloc *a, bool put, char *lin, Loc lloc, uint64_t rem_off, uint64_t
     const bool lin_dev = lloc == LOC_DEVICE;
     const bool dma_pick = dir_tuning(put).variant == XFER_DMA;
     // Small blocking ops go to the resident copy service.
-    if (lin_dev && a->all_dev_ok && !async && len <= s.svc_limit(a) && !dma_pick) {
+    if (lin_dev && a->all_dev_ok && !async && len <= s.cfg.svc_limit(a) && !dma_pick) {
         const int rc = xfer_service(a, put, lin, rem_off, len);
         if (rc == 0) return 0;
         if (rc == -2) return -1;
         OCM_WARN("copy service failed (%s); falling back to launches", last_error());
-        s.svc_max = 0;
+        s.cfg.svc_max = 0;
     }
     // Async ops queue on the allocation's lane; blocking ops on the library stream
     // after the allocation's queued async work.
@@ -341,7 +341,7 @@ int xfer(lib_alloc *a, bool put, char *lin, Loc lloc, uint64_t rem_off, uint64_t
     // profiles/pcie_stream_r03.json). OCM_HOST_ENGINE=sdma keeps the runtime's
     // copy engines for host-tier pairs as a measured baseline.
     const bool use_kernel =
-        lin_dev && !dma_pick && (a->any_gpu || s.host_engine_kernel || len <= s.host_kernel_max);
+        lin_dev && !dma_pick && (a->any_gpu || s.cfg.host_engine_kernel || len <= s.cfg.host_kernel_max);
     if (!use_kernel) return xfer_dma(a, put, lin, lloc, rem_off, len, st, async);
     if (!put && a->all_gpu && dir_tuning(false).variant == XFER_PUSH) return xfer_push(a, lin, rem_off, len, st, async);
     return xfer_kernel(a, put, lin, rem_off, len, st, async, done);
