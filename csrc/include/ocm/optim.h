@@ -21,6 +21,7 @@ struct AdamArgs {
     uint64_t m_off, v_off;           // byte offsets of element 0's exp_avg / exp_avg_sq (16-byte aligned)
     uint64_t n;                      // elements
     float b1, b2, eps, wd;           // betas, eps, L2 weight decay
+    float omb1, omb2;                // 1 - b1, 1 - b2: computed in double by the caller, rounded once
     float step_size;                 // lr / (1 - b1^t)
     float inv_sqrt_bc2;              // 1 / sqrt(1 - b2^t)
     uint32_t bf16;                   // 1: p and g are bf16; fp32 master weights at w_off in the state

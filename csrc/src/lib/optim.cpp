@@ -2,8 +2,10 @@
 // not part of the ABI): p/g are this GPU's parameters and gradients (n floats),
 // exp_avg / exp_avg_sq of element 0 sit at byte offsets m_off / v_off of the
 // remote half. hp = {b1, b2, eps, weight_decay, step_size, 1/sqrt(bias_correction2),
-// adamw_decay}: adamw_decay = 1 - lr * weight_decay selects AdamW (decoupled decay;
-// weight_decay then unused), NaN selects Adam with the L2 term.
+// adamw_decay, 1 - b1, 1 - b2}: adamw_decay = 1 - lr * weight_decay selects AdamW
+// (decoupled decay; weight_decay then unused), NaN selects Adam with the L2 term. The two
+// complements are the caller's, computed in double from the exact betas like the bias
+// corrections: 1.f - float(0.999) is 1.3e-5 short of float(0.001).
 // Queued on `stream` (e.g. torch's current stream); no host wait.
 #include <cmath>
 
@@ -21,7 +23,7 @@ namespace {
 // word the errors, under their own names.
 enum AdamBad { ADAM_OK = 0, ADAM_NO_GPU, ADAM_NO_PAIR, ADAM_EXTENTS, ADAM_STRIPE };
 
-AdamBad adam_prepare(ocm_alloc_t a, const float hp[7], bool bf16, AdamArgs *x) {
+AdamBad adam_prepare(ocm_alloc_t a, const float hp[9], bool bf16, AdamArgs *x) {
     if (S().device < 0) return ADAM_NO_GPU;
     if (!is_pair(a->kind) || a->ext.empty() || !a->all_dev_ok) return ADAM_NO_PAIR;
     if (a->ext.size() > (size_t)kXferMaxExtents) return ADAM_EXTENTS;
@@ -35,6 +37,8 @@ AdamBad adam_prepare(ocm_alloc_t a, const float hp[7], bool bf16, AdamArgs *x) {
     x->inv_sqrt_bc2 = hp[5];
     x->decoupled = std::isnan(hp[6]) ? 0u : 1u;  // NaN: L2 Adam; else AdamW's weight multiplier
     x->decay = hp[6];
+    x->omb1 = hp[7];
+    x->omb2 = hp[8];
     x->host_state = (!a->any_gpu && !a->any_net) ? 1u : 0u;
     x->bf16 = bf16 ? 1u : 0u;
     return ADAM_OK;
@@ -46,7 +50,7 @@ bool fits(ocm_alloc_t a, uint64_t off, uint64_t n) {
 }
 
 int adam_common(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64_t w_off, uint64_t m_off, uint64_t v_off,
-                const float hp[7], void *stream, bool bf16) {
+                const float hp[9], void *stream, bool bf16) {
     State &s = S();
     if (!a || !p || !g || !hp) OCM_FAIL(-1, "ocm_x_adam: null argument");
     AdamArgs x;
@@ -80,14 +84,14 @@ int adam_common(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64_t w_of
 extern "C" {
 
 int ocm_x_adam(ocm_alloc_t a, float *p, const float *g, uint64_t n, uint64_t m_off, uint64_t v_off,
-               const float hp[7], void *stream) {
+               const float hp[9], void *stream) {
     return adam_common(a, p, g, n, 0, m_off, v_off, hp, stream, false);
 }
 
 // Mixed precision: p / g are bf16 on this GPU, the fp32 master weights sit at
 // byte offset w_off of the remote half next to the moments.
 int ocm_x_adam_bf16(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64_t w_off, uint64_t m_off,
-                    uint64_t v_off, const float hp[7], void *stream) {
+                    uint64_t v_off, const float hp[9], void *stream) {
     return adam_common(a, p, g, n, w_off, m_off, v_off, hp, stream, true);
 }
 
@@ -95,7 +99,7 @@ int ocm_x_adam_bf16(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64_t 
 // segment): p[i] / g[i] of n[i] elements, state at w_off[i] (bf16 only),
 // m_off[i], v_off[i] of the remote half. Same hp as ocm_x_adam.
 int ocm_x_adam_multi(ocm_alloc_t a, int count, void *const *p, const void *const *g, const uint64_t *n,
-                     const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[7],
+                     const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[9],
                      int bf16, void *stream) {
     State &s = S();
     if (!a || count < 0 || (count && (!p || !g || !n || !m_off || !v_off || (bf16 && !w_off))) || !hp)

@@ -270,13 +270,17 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
 
 
 def _adam_hp(hp) -> tuple:
-    """(b1, b2, eps, weight_decay, step_size, 1/sqrt(bias_correction2)[, decay]) -> 7 floats.
-    decay is AdamW's weight multiplier 1 - lr * weight_decay; NaN (the default) selects
-    L2-regularised Adam."""
+    """(b1, b2, eps, weight_decay, step_size, 1/sqrt(bias_correction2)[, decay]) -> the 9 floats
+    of the ocm_x_adam* hooks: those 7, then 1 - b1 and 1 - b2. decay is AdamW's weight multiplier
+    1 - lr * weight_decay; NaN (the default) selects L2-regularised Adam. The complements are
+    taken here, in double, so the kernel gets them rounded once (1.f - float(0.999) is 1.3e-5
+    short of float(0.001))."""
     hp = tuple(float(x) for x in hp)
     if len(hp) not in (6, 7):
         raise ValueError("Adam hyper-parameters: 6 values (Adam) or 7 (AdamW decay multiplier last)")
-    return hp if len(hp) == 7 else hp + (float("nan"),)
+    if len(hp) == 6:
+        hp += (float("nan"),)
+    return hp + (1.0 - hp[0], 1.0 - hp[1])
 
 
 def last_error() -> str:
@@ -927,11 +931,13 @@ class Allocation:
         updated directly; bfloat16 p/g need w_off, the fp32 master weights in the remote half,
         which the update runs on (ocm_x_adam_bf16). hp = (b1, b2, eps, weight_decay, step_size,
         1/sqrt(bias_correction2)[, adamw_decay]); adamw_decay = 1 - lr * weight_decay selects AdamW.
+        b1 and b2 are the exact (Python float) betas: 1 - b1 and 1 - b2 are taken from them in
+        double and reach the kernel as fp32 values of their own.
         Queued on `stream` (default: torch's current stream)."""
         import torch
 
         hp = _adam_hp(hp)
-        h = (ctypes.c_float * 7)(*hp)
+        h = (ctypes.c_float * 9)(*hp)
         pp, gp, st = ctypes.c_void_p(p.data_ptr()), ctypes.c_void_p(g.data_ptr()), self._stream_handle(stream)
         if p.dtype == torch.bfloat16:
             if w_off is None or g.dtype != torch.bfloat16:
@@ -958,7 +964,7 @@ class Allocation:
         rc = self._c.lib.ocm_x_adam_multi(
             self.handle, k, arr_v(*[t.data_ptr() for t in ps]), arr_v(*[t.data_ptr() for t in gs]),
             arr_u(*[t.numel() for t in ps]), arr_u(*(w_offs or [0] * k)), arr_u(*m_offs), arr_u(*v_offs),
-            (ctypes.c_float * 7)(*hp), 1 if bf16 else 0, self._stream_handle(stream))
+            (ctypes.c_float * 9)(*hp), 1 if bf16 else 0, self._stream_handle(stream))
         if rc != 0:
             raise OcmError("ocm_x_adam_multi: " + last_error())
 
