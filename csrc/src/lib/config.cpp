@@ -89,6 +89,11 @@ Config config_from_env() {
     c.svc_prearm = env_bool("OCM_SERVICE_PREARM", c.svc_prearm);
     c.svc_arm_window_ns = env_scaled("OCM_SERVICE_PREARM_MS", c.svc_arm_window_ns, 1000000, 0);
     c.svc_inline = env_bool("OCM_SERVICE_INLINE", c.svc_inline);
+
+    c.adam_host = env_bool("OCM_ADAM_HOST", c.adam_host);
+    c.adam_host_grid = env_int("OCM_ADAM_HOST_GRID", c.adam_host_grid);
+    c.adam_host_vec = env_int("OCM_ADAM_HOST_VEC", c.adam_host_vec);
+    c.adam_grid = env_int("OCM_ADAM_GRID", c.adam_grid);
     return c;
 }
 

@@ -166,6 +166,21 @@ struct Config {
     bool svc_prearm = false;
     uint64_t svc_arm_window_ns = 20 * 1000000ull;
     bool svc_inline = true;  // OCM_SERVICE_INLINE: a cold start carries its solo request in the kernel arguments
+
+    // ---- fused Adam (ocm/optim.h: adam_launch_shape takes these as AdamKnobs)
+    // Host-tier state in one extent, every offset within 4 GiB of its base: the PCIe
+    // variant of the kernel (OCM_ADAM_HOST=0 keeps the generic one).
+    bool adam_host = true;
+    // 128 workgroups: 91 GiB/s of state (both directions of the link at once) against
+    // 82 for the HBM-tuned full-chip grid; 64-160 are equal, 192 and up lose
+    // (profiles/adam_host_probe_r03.json). OCM_ADAM_HOST_GRID; 0: the HBM grid rule.
+    int adam_host_grid = 128;
+    // Vectors in flight per lane of the fp32 PCIe variant (OCM_ADAM_HOST_VEC: 2, 8, anything
+    // else 4). On HBM state, 4 vectors per lane and 2 workgroups per CU are the fastest
+    // (1.40 ms for 256 Mi params; 8 vectors per lane is 4x slower: profiles/optim_offload_r01.json
+    // "adam_kernel_sweep"), and the generic variant is built with those alone.
+    int adam_host_vec = 4;
+    int adam_grid = 0;  // OCM_ADAM_GRID > 0: this many workgroups per tensor on every variant (measurements)
 };
 
 // The configuration the environment asks for: a pure function of it, so a second

@@ -17,10 +17,9 @@ using namespace ocmlib;
 
 namespace {
 
-// What both entry points do before they launch: check that a kernel on this GPU can
-// address the pair's remote half, and fill the fields every launch shares (the extent
-// table and stripe shift, the hyper-parameters, where the state lives). The callers
-// word the errors, under their own names.
+// Before any launch: check that a kernel on this GPU can address the pair's remote
+// half, and fill the fields every launch shares (the extent table and stripe shift,
+// the hyper-parameters, where the state lives). adam_run words the errors.
 enum AdamBad { ADAM_OK = 0, ADAM_NO_GPU, ADAM_NO_PAIR, ADAM_EXTENTS, ADAM_STRIPE };
 
 AdamBad adam_prepare(ocm_alloc_t a, const float hp[9], bool bf16, AdamArgs *x) {
@@ -49,79 +48,40 @@ bool fits(ocm_alloc_t a, uint64_t off, uint64_t n) {
     return n <= (UINT64_MAX >> 3) && off <= a->remote_bytes && 4 * n <= a->remote_bytes - off;
 }
 
-int adam_common(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64_t w_off, uint64_t m_off, uint64_t v_off,
-                const float hp[9], void *stream, bool bf16) {
+// The one path behind the three entry points: `count` tensors, kAdamMaxTensors per launch.
+// `who` names the caller in the messages; the list entry point (`multi`) words some of them
+// its own way and names the tensor at fault. Every tensor is checked before the first
+// launch: a bad one never leaves some parameters a step ahead of the others.
+int adam_run(const char *who, bool multi, ocm_alloc_t a, int count, void *const *p, const void *const *g,
+             const uint64_t *n, const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[9],
+             bool bf16, void *stream) {
     State &s = S();
-    if (!a || !p || !g || !hp) OCM_FAIL(-1, "ocm_x_adam: null argument");
-    AdamArgs x;
-    switch (adam_prepare(a, hp, bf16, &x)) {
-    case ADAM_NO_GPU: OCM_FAIL(-1, "ocm_x_adam needs a GPU");
-    case ADAM_NO_PAIR:
-        OCM_FAIL(-1, "ocm_x_adam needs a remote half this GPU can address (HBM or host tier, not another node)");
-    case ADAM_EXTENTS: OCM_FAIL(-1, "ocm_x_adam: too many extents");
-    case ADAM_STRIPE: OCM_FAIL(-1, "ocm_x_adam: stripe unit %llu unusable", (unsigned long long)a->stripe_unit);
-    case ADAM_OK: break;
-    }
-    if (!fits(a, m_off, n) || !fits(a, v_off, n) || (bf16 && !fits(a, w_off, n)))
-        OCM_FAIL(-1, "ocm_x_adam: state range exceeds the remote half (%zu bytes)", a->remote_bytes);
-    x.p = static_cast<float *>(p);
-    x.g = static_cast<const float *>(g);
-    x.w_off = w_off;
-    x.m_off = m_off;
-    x.v_off = v_off;
-    x.n = n;
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    if (wait_alloc(a) != 0) return -1;  // queued async ops on this allocation come first
-    DeviceGuard dg(s.device);
-    before_launch();
-    const hipError_t e = adam_remote_launch(x, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) OCM_FAIL(-1, "ocm_x_adam launch: %s", hipGetErrorString(e));
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ocm_x_adam(ocm_alloc_t a, float *p, const float *g, uint64_t n, uint64_t m_off, uint64_t v_off,
-               const float hp[9], void *stream) {
-    return adam_common(a, p, g, n, 0, m_off, v_off, hp, stream, false);
-}
-
-// Mixed precision: p / g are bf16 on this GPU, the fp32 master weights sit at
-// byte offset w_off of the remote half next to the moments.
-int ocm_x_adam_bf16(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64_t w_off, uint64_t m_off,
-                    uint64_t v_off, const float hp[9], void *stream) {
-    return adam_common(a, p, g, n, w_off, m_off, v_off, hp, stream, true);
-}
-
-// Many parameters per launch (32 per kernel, descriptors in the kernarg
-// segment): p[i] / g[i] of n[i] elements, state at w_off[i] (bf16 only),
-// m_off[i], v_off[i] of the remote half. Same hp as ocm_x_adam.
-int ocm_x_adam_multi(ocm_alloc_t a, int count, void *const *p, const void *const *g, const uint64_t *n,
-                     const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[9],
-                     int bf16, void *stream) {
-    State &s = S();
-    if (!a || count < 0 || (count && (!p || !g || !n || !m_off || !v_off || (bf16 && !w_off))) || !hp)
-        OCM_FAIL(-1, "ocm_x_adam_multi: null argument");
+    if (!a || count < 0 || (count && (!p || !g || !n || !m_off || !v_off || (bf16 && !w_off))) || !hp ||
+        (!multi && (!p[0] || !g[0])))
+        OCM_FAIL(-1, "%s: null argument", who);
     AdamMultiArgs x;
     std::memset(&x, 0, sizeof(x));
-    switch (adam_prepare(a, hp, bf16 != 0, &x.c)) {
-    case ADAM_NO_GPU: OCM_FAIL(-1, "ocm_x_adam_multi needs a GPU");
-    case ADAM_NO_PAIR:
-    case ADAM_EXTENTS: OCM_FAIL(-1, "ocm_x_adam_multi needs a remote half this GPU can address");
-    case ADAM_STRIPE: OCM_FAIL(-1, "ocm_x_adam_multi: stripe unit unusable");
+    const char *const which = multi ? "" : " (HBM or host tier, not another node)";
+    switch (adam_prepare(a, hp, bf16, &x.c)) {
+    case ADAM_NO_GPU: OCM_FAIL(-1, "%s needs a GPU", who);
+    case ADAM_EXTENTS:
+        if (!multi) OCM_FAIL(-1, "%s: too many extents", who);
+        [[fallthrough]];
+    case ADAM_NO_PAIR: OCM_FAIL(-1, "%s needs a remote half this GPU can address%s", who, which);
+    case ADAM_STRIPE:
+        if (multi) OCM_FAIL(-1, "%s: stripe unit unusable", who);
+        OCM_FAIL(-1, "%s: stripe unit %llu unusable", who, (unsigned long long)a->stripe_unit);
     case ADAM_OK: break;
     }
-    // Every tensor is checked before the first launch: a bad one never leaves
-    // some parameters a step ahead of the others.
     for (int i = 0; i < count; i++) {
-        if (!p[i] || !g[i]) OCM_FAIL(-1, "ocm_x_adam_multi: tensor %d has no data", i);
-        if (!fits(a, m_off[i], n[i]) || !fits(a, v_off[i], n[i]) || (bf16 && !fits(a, w_off[i], n[i])))
-            OCM_FAIL(-1, "ocm_x_adam_multi: tensor %d state range exceeds the remote half", i);
+        if (!p[i] || !g[i]) OCM_FAIL(-1, "%s: tensor %d has no data", who, i);
+        if (fits(a, m_off[i], n[i]) && fits(a, v_off[i], n[i]) && (!bf16 || fits(a, w_off[i], n[i]))) continue;
+        if (multi) OCM_FAIL(-1, "%s: tensor %d state range exceeds the remote half", who, i);
+        OCM_FAIL(-1, "%s: state range exceeds the remote half (%zu bytes)", who, a->remote_bytes);
     }
     std::lock_guard<std::recursive_mutex> lk(s.mu);
-    if (wait_alloc(a) != 0) return -1;
+    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
+    if (wait_alloc(a) != 0) return -1;  // queued async ops on this allocation come first
     DeviceGuard dg(s.device);
     before_launch();
     for (int k0 = 0; k0 < count; k0 += kAdamMaxTensors) {
@@ -130,10 +90,38 @@ int ocm_x_adam_multi(ocm_alloc_t a, int count, void *const *p, const void *const
             const int i = k0 + (int)j;
             x.t[j] = AdamTensor{p[i], g[i], n[i], bf16 ? w_off[i] : 0, m_off[i], v_off[i]};
         }
-        const hipError_t e = adam_remote_multi_launch(x, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) OCM_FAIL(-1, "ocm_x_adam_multi launch: %s", hipGetErrorString(e));
+        const hipError_t e = adam_remote_launch(x, knobs, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One tensor: the count = 1 case of ocm_x_adam_multi, under its own name.
+int ocm_x_adam(ocm_alloc_t a, float *p, const float *g, uint64_t n, uint64_t m_off, uint64_t v_off,
+               const float hp[9], void *stream) {
+    void *const pp = p;
+    const void *const gp = g;
+    return adam_run("ocm_x_adam", false, a, 1, &pp, &gp, &n, nullptr, &m_off, &v_off, hp, false, stream);
+}
+
+// Mixed precision: p / g are bf16 on this GPU, the fp32 master weights sit at
+// byte offset w_off of the remote half next to the moments.
+int ocm_x_adam_bf16(ocm_alloc_t a, void *p, const void *g, uint64_t n, uint64_t w_off, uint64_t m_off,
+                    uint64_t v_off, const float hp[9], void *stream) {
+    return adam_run("ocm_x_adam", false, a, 1, &p, &g, &n, &w_off, &m_off, &v_off, hp, true, stream);
+}
+
+// Many parameters per launch (32 per kernel, descriptors in the kernarg
+// segment): p[i] / g[i] of n[i] elements, state at w_off[i] (bf16 only),
+// m_off[i], v_off[i] of the remote half. Same hp as ocm_x_adam.
+int ocm_x_adam_multi(ocm_alloc_t a, int count, void *const *p, const void *const *g, const uint64_t *n,
+                     const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[9],
+                     int bf16, void *stream) {
+    return adam_run("ocm_x_adam_multi", true, a, count, p, g, n, w_off, m_off, v_off, hp, bf16 != 0, stream);
 }
 
 }  // extern "C"

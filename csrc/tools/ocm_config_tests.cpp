@@ -41,7 +41,8 @@ const char *const kVars[] = {
     "OCM_SERVICE_HOST_GET_NARROW_MIN", "OCM_SERVICE_HOST_GET_WIDTH", "OCM_SERVICE_PARK_KERNEL", "OCM_SERVICE_IDLE_US",
     "OCM_SERVICE_DEGRADED_IDLE_US", "OCM_SERVICE_LONE_US", "OCM_SERVICE_ROSTER_WAIT_US", "OCM_SERVICE_TIMEOUT_MS",
     "OCM_SERVICE_DRAIN_MS", "OCM_SERVICE_BOX_RESET", "OCM_SERVICE_RELAUNCH_QUERY", "OCM_SERVICE_PREARM",
-    "OCM_SERVICE_PREARM_MS", "OCM_SERVICE_INLINE"};
+    "OCM_SERVICE_PREARM_MS", "OCM_SERVICE_INLINE", "OCM_ADAM_HOST", "OCM_ADAM_HOST_GRID", "OCM_ADAM_HOST_VEC",
+    "OCM_ADAM_GRID"};
 
 void clear_env() {
     for (const char *k : kVars) unsetenv(k);
@@ -70,7 +71,7 @@ Fields fields(const Config &c) {
             F(svc_host_tile_max), F(svc_host_get_narrow_min), F(svc_host_get_width), F(svc_park_kernel),
             F(svc_idle_ticks), F(svc_degraded_idle_ticks), F(svc_lone_ticks), F(svc_roster_wait_ns), F(svc_timeout_ns),
             F(svc_drain_ns), F(svc_box_reset_always), F(svc_relaunch_query), F(svc_prearm), F(svc_arm_window_ns),
-            F(svc_inline)};
+            F(svc_inline), F(adam_host), F(adam_host_grid), F(adam_host_vec), F(adam_grid)};
 #undef F
 }
 
@@ -89,7 +90,8 @@ const Fields kDefaults = {
     {"svc_park_kernel", 0}, {"svc_idle_ticks", 100 * 50}, {"svc_degraded_idle_ticks", 100 * 5000},
     {"svc_lone_ticks", 100 * 2000}, {"svc_roster_wait_ns", 200000}, {"svc_timeout_ns", 10000000000ull},
     {"svc_drain_ns", 10000000000ull}, {"svc_box_reset_always", 0}, {"svc_relaunch_query", 0}, {"svc_prearm", 0},
-    {"svc_arm_window_ns", 20000000}, {"svc_inline", 1}};
+    {"svc_arm_window_ns", 20000000}, {"svc_inline", 1}, {"adam_host", 1}, {"adam_host_grid", 128}, {"adam_host_vec", 4},
+    {"adam_grid", 0}};
 
 void expect_fields(const char *what, const Config &c, const Fields &want) {
     const Fields got = fields(c);
@@ -107,7 +109,9 @@ void test_defaults() {
     expect_fields("nothing set", parse(), kDefaults);
     expect_fields("Config{}", Config{}, kDefaults);
     // an empty variable counts as unset
-    expect_fields("empty variables", parse({{"OCM_SERVICE_MAX", ""}, {"OCM_PINNED_KEEP", ""}, {"OCM_SERVICE_BLOCKS", ""}}),
+    expect_fields("empty variables",
+                  parse({{"OCM_SERVICE_MAX", ""}, {"OCM_PINNED_KEEP", ""}, {"OCM_SERVICE_BLOCKS", ""}, {"OCM_ADAM_HOST", ""},
+                         {"OCM_ADAM_HOST_GRID", ""}, {"OCM_ADAM_HOST_VEC", ""}, {"OCM_ADAM_GRID", ""}}),
                   kDefaults);
     if (failures == before) std::printf("PASS defaults\n");
 }
@@ -202,6 +206,11 @@ void test_determinism() {
               c.svc_host_tile_shift_get == 12 && c.svc_host_tile_shift_put == 13 && !c.svc_queue_aql,
           "the variables set were not all taken");
     expect_fields("after unsetting them", parse(), kDefaults);
+    // the fused Adam knobs, which the launcher used to read once per process
+    Config d = parse({{"OCM_ADAM_HOST", "0"}, {"OCM_ADAM_HOST_GRID", "64"}, {"OCM_ADAM_HOST_VEC", "8"}, {"OCM_ADAM_GRID", "7"}});
+    CHECK(!d.adam_host && d.adam_host_grid == 64 && d.adam_host_vec == 8 && d.adam_grid == 7, "OCM_ADAM_*: first parse");
+    d = parse({{"OCM_ADAM_HOST", "1"}, {"OCM_ADAM_HOST_GRID", "0"}, {"OCM_ADAM_HOST_VEC", "2"}});
+    CHECK(d.adam_host && d.adam_host_grid == 0 && d.adam_host_vec == 2 && d.adam_grid == 0, "OCM_ADAM_*: second parse");
     if (failures == before) std::printf("PASS determinism\n");
 }
 

@@ -20,7 +20,7 @@ k, and the write-back of chunk k overlaps the update of chunk k + 1. Nothing wai
 on the host inside a step.
 
 mode="fused" (default on a GPU) skips the staging altogether: one gfx950 kernel
-per parameter (ocm_x_adam, csrc/src/kernels/optim.hip) reads p and g from local
+launch per 32 parameters (ocm_x_adam_multi, csrc/src/kernels/optim.hip) reads p and g from local
 HBM and exp_avg / exp_avg_sq straight from the remote half (peer HBM over xGMI or
 the pinned host tier), updates in registers and writes everything back: one pass,
 no copies, no extra local HBM traffic. bfloat16 parameters keep fp32 master

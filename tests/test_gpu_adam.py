@@ -1,10 +1,9 @@
-"""The fused Adam kernels (csrc/src/kernels/optim.hip) through Allocation.adam and
-Allocation.adam_multi, every path against the fp64 oracle of tests/adam_cases.py:
+"""The fused Adam kernel (csrc/src/kernels/optim.hip, adam_multi_kernel) through
+Allocation.adam (one tensor: the count = 1 case) and Allocation.adam_multi, every variant
+against the fp64 oracle of tests/adam_cases.py:
 
-  adam_remote_kernel       single fp32 on HBM and striped state
-  adam_host_kernel         single fp32 on host-tier state
-  adam_remote_bf16_kernel  single bf16 on all three
-  adam_multi_kernel        fp32 / bf16, generic (HBM, striped) and host variants
+  <fp32 | bf16, generic>  HBM and striped state
+  <fp32 | bf16, host>     host-tier state in one extent
 
 with lengths from one tail element to a second grid-stride pass, state offsets that are
 16-byte but not 256-byte aligned, stripe-unit boundaries inside the arrays, both orders of the
@@ -68,8 +67,7 @@ def _alloc(c, state, nbytes):
 def second_pass_length(host_kernel):
     """A length that reaches the grid-stride loop's second pass and ends on a 3-element tail:
     in that pass some of a lane's four vectors are live and some are past the end. The host
-    kernels (adam_host_kernel, adam_multi_kernel<.., true>) run 128 workgroups, the others two
-    per CU."""
+    variants (adam_multi_kernel<.., true>) run 128 workgroups, the generic ones two per CU."""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     per_pass = 128 * 4096 if host_kernel else 2 * cus * 4096
     return per_pass + 4 * (256 + 17) + 3
@@ -248,12 +246,10 @@ def _record(path):
 
 @pytest.mark.parametrize("state", ["hbm", "host", "striped"])
 def test_every_path_against_the_oracle(mesh_factory, state):
-    big = second_pass_length(state == "host")
-    # single bf16 has no host kernel: on host-tier state too it is adam_remote_bf16_kernel's grid
-    big_bf16 = second_pass_length(False)
+    big = second_pass_length(state == "host")  # fp32 and bf16 alike: both have a host variant
     msizes, mskip = _multi_sizes(big)
     with _client(mesh_factory, state) as c:
-        a = _alloc(c, state, max(Layout(s, "mvw").nbytes for s in (msizes, [big_bf16] + SMALL)))
+        a = _alloc(c, state, max(Layout(s, "mvw").nbytes for s in (msizes, [big] + SMALL)))
         try:
             for bf16 in (False, True):
                 kind = "bf16" if bf16 else "fp32"
@@ -261,7 +257,7 @@ def test_every_path_against_the_oracle(mesh_factory, state):
                 # round as well, with exp_avg behind exp_avg_sq (bf16: the master between them)
                 long_set, short_set = ("adamw", "fast_l2") if bf16 else ("default_l2", "adamw")
                 fwd, rev = ("mvw", "vwm") if bf16 else ("mv", "vm")
-                run_case(a, f"single-{kind}/{state}", [big_bf16 if bf16 else big] + SMALL, long_set, bf16, False, fwd)
+                run_case(a, f"single-{kind}/{state}", [big] + SMALL, long_set, bf16, False, fwd)
                 run_case(a, f"single-{kind}/{state}", SMALL, short_set, bf16, False, rev)
                 # multi: the long tensor gets (nearly) the whole grid, gx = min(want, tuned grid *
                 # biggest / total), and is longer than one pass of it

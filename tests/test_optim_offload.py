@@ -222,7 +222,7 @@ def test_flatten_params_keeps_dtypes_honest():
 @pytest.mark.gpu
 @pytest.mark.parametrize("flags", [0, api.OCM_ALLOC_HOST_TIER])
 def test_single_tensor_adam_matches_torch(mesh_factory, flags):
-    """Allocation.adam (ocm_x_adam, one launch for one tensor) with the moments in
+    """Allocation.adam (ocm_x_adam: the kernel launched for a list of one) with the moments in
     another daemon's HBM or in the pinned host tier (the PCIe variant of the
     kernel), a length that leaves a 3-element tail, against torch.optim.Adam."""
     import math
