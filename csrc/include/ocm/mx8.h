@@ -55,6 +55,12 @@ OCM_MX8_HD inline uint32_t mx8_pow2_bits(int k) { return (uint32_t)(k + 127) << 
 
 inline size_t mx8_record_bytes(uint64_t elems) { return (size_t)(elems + elems / kMx8Group); }
 
+// The wave-tile of the converting kernels (ocm/quant.h, ocm/quant_strided.h): 2048
+// elements, 4 KiB of source, 2 KiB of codes, 64 scale bytes.
+constexpr uint32_t kQuantTileShift = 11;
+constexpr uint32_t kQuantTileElems = 1u << kQuantTileShift;
+OCM_MX8_HD inline uint64_t quant_tile_count(uint64_t elems) { return (elems + kQuantTileElems - 1) >> kQuantTileShift; }
+
 // ---- plain C++ codec ----
 
 inline float mx8_bits_float(uint32_t b) {

@@ -10,15 +10,12 @@
 // element type (enum ocm_quant_dtype). XferBatchArgs carries them unchanged
 // (tile_shift is unused), so large lists take the batch path's staged upload.
 #pragma once
+#include "ocm/mx8.h"
 #include "ocm/xfer.h"
 
 namespace ocm {
 
-constexpr uint32_t kQuantTileShift = 11;  // 2048 elements: 4 KiB of source, 2 KiB of codes, 64 scale bytes
-constexpr uint32_t kQuantTileElems = 1u << kQuantTileShift;
-
-inline uint64_t quant_tile_count(uint64_t elems) { return (elems + kQuantTileElems - 1) >> kQuantTileShift; }
-// Fills first_tile, returns total tiles.
+// Fills first_tile (quant_tile_count of ocm/mx8.h per op), returns total tiles.
 inline uint64_t xfer_quant_plan(XferBatchOp *ops, uint32_t n) {
     return list_plan(ops, n, [](const XferBatchOp &op) { return quant_tile_count(op.len); });
 }
@@ -26,5 +23,10 @@ inline uint64_t xfer_quant_plan(XferBatchOp *ops, uint32_t n) {
 // Stores: nontemporal (t.nontemporal), except that puts into a pool wholly in the
 // pinned host tier (a.host_tier) store plain, as the batch kernel's host shape does.
 hipError_t xfer_quant_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream);
+
+// Strided converting lists (ocm/quant_strided.h: the descriptor, the row-relative tile
+// rule and the host plan): one launch, one record per row; stores as above.
+struct XferQuantStridedArgs;
+hipError_t xfer_quant_strided_launch(const XferQuantStridedArgs &a, const XferTuning &t, hipStream_t stream);
 
 }  // namespace ocm

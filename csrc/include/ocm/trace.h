@@ -25,6 +25,8 @@ struct OpCounters {
     uint64_t n_strided = 0, n_strided_ops = 0, bytes_strided = 0;
     // accumulates (ocm_copy_onesided_accumulate): calls, ops, accumulator bytes updated (4 * elems)
     uint64_t n_acc = 0, n_acc_ops = 0, bytes_acc = 0;
+    // strided converting ops (ocm_copy_onesided_quant_strided): calls, ops, 16-bit source bytes, record bytes
+    uint64_t n_quant_strided = 0, n_quant_strided_ops = 0, bytes_quant_strided_src = 0, bytes_quant_strided_wire = 0;
 };
 
 bool trace_enabled();  // OCM_TRACE=0 disables the roctx ranges

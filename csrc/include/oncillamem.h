@@ -172,6 +172,30 @@ struct ocm_quant_params {
 /* Bytes of the record of `elems` elements: elems + elems / 32. */
 size_t ocm_quant_bytes(uint64_t elems);
 int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags);
+/* Strided converting copies (layer-major KV caches): by definition the
+ * ocm_copy_onesided_quant list with one op per row. Row r of an op is the converting op
+ * (local_offset + r * local_stride, remote_offset + r * remote_stride, row_elems,
+ * op_flag, dtype), r = 0 .. rows - 1: every row has a record of its own, its codes and
+ * then its scale bytes, so a later ocm_copy_onesided_quant get can read one row of what
+ * a strided put wrote. Ops of one call and rows of one op run concurrently, puts and
+ * gets mixed, as ONE gfx950 launch when the local half is device memory. Per op: dtype
+ * known, row_elems % 32 == 0 and row_elems < 2^31, rows < 2^32, local_offset and
+ * local_stride multiples of 16, remote_offset and remote_stride multiples of 32, with
+ * rows > 1 local_stride >= 2 * row_elems and remote_stride >= row_elems + row_elems / 32,
+ * and the last row's end inside its half on both sides; an op with rows == 0 or
+ * row_elems == 0 does nothing. flags and ordering as for ocm_copy_onesided_batch
+ * (OCM_BATCH_ASYNC, ocm_wait, ocm_stream_wait/signal). */
+struct ocm_quant_strided_params {
+    uint64_t local_offset;   /* first element of row 0 in the local half (bytes) */
+    uint64_t remote_offset;  /* first byte of row 0's record in the remote half */
+    uint64_t row_elems;      /* 16-bit elements per row */
+    uint64_t rows;
+    uint64_t local_stride;   /* bytes from one row's start to the next, local side */
+    uint64_t remote_stride;  /* bytes from one row's record to the next, remote side */
+    int32_t  op_flag;        /* 1 = put (encode), 0 = get (decode) */
+    uint32_t dtype;          /* enum ocm_quant_dtype */
+};
+int ocm_copy_onesided_quant_strided(ocm_alloc_t a, const struct ocm_quant_strided_params *ops, int n_ops, int flags);
 /* Strided one-sided copies (2-D put / get): row r of an op moves row_bytes bytes between
  * local[local_offset + r * local_stride] and remote[remote_offset + r * remote_stride],
  * r = 0 .. rows - 1, in the direction of ocm_copy_onesided (op_flag 1 = put). Ops of one

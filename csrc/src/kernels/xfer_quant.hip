@@ -1,5 +1,6 @@
 // Converting one-sided ops: bf16 / fp16 <-> MXFP8 records (ocm/mx8.h) as the bytes
-// cross to the remote half, one launch per list; see ocm/quant.h for the plan.
+// cross to the remote half, one launch per list; see ocm/quant.h for the plan. The
+// tile bodies (put_tile, get_tile) are in quant_tile.h, shared with xfer_quant_strided.hip.
 //
 // A wave-tile is 2048 elements, done in two rounds of 1024. In a round lane l owns
 // elements [16 l, 16 l + 16): two 16-byte vectors of source, one 16-byte vector of
@@ -15,129 +16,13 @@
 
 #include "ocm/mx8.h"
 #include "ocm/quant.h"
+#include "quant_tile.h"
 #include "xfer_copy.h"
 #include "xfer_host.h"
 
 namespace ocm {
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr uint32_t kRoundElems = 1024;  // 64 lanes x 16 elements
-
-template <bool BF16>
-__device__ __forceinline__ float widen16(uint32_t h) {
-    if constexpr (BF16)
-        return __builtin_bit_cast(float, h << 16);
-    else
-        return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
-}
-
-// Round to nearest even into the element type.
-template <bool BF16>
-__device__ __forceinline__ uint32_t narrow16(float f) {
-    if constexpr (BF16) {
-        const uint32_t b = __builtin_bit_cast(uint32_t, f);
-        if ((b & 0x7fffffffu) > 0x7f800000u) return (b >> 16) | 0x40u;
-        return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-    } else {
-        return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
-    }
-}
-
-// One put tile: `ne` elements (a multiple of 32, at most 2048) from `lin` into codes
-// at striped offset `codes` and scale bytes at `scales`. sw: this wave's 64 bytes of LDS.
-template <bool BF16, bool NT>
-__device__ __forceinline__ void put_tile(const XferBatchArgs &a, const char *lin, uint64_t codes, uint64_t scales,
-                                         uint32_t ne, uint32_t lane, uint8_t *sw) {
-#pragma unroll
-    for (uint32_t r = 0; r < 2; r++) {
-        const uint32_t el = r * kRoundElems + lane * 16;
-        const bool active = el < ne;  // a lane pair (one group) is in or out together
-        u32x4 v[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        if (active) {
-            const u32x4 *s = reinterpret_cast<const u32x4 *>(lin + 2ull * el);
-            v[0] = __builtin_nontemporal_load(s);
-            v[1] = __builtin_nontemporal_load(s + 1);
-        }
-        float x[16];
-        uint32_t amax = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t w = v[k >> 2][k & 3];
-            x[2 * k] = widen16<BF16>(w & 0xffffu);
-            x[2 * k + 1] = widen16<BF16>(w >> 16);
-        }
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const uint32_t ab = __builtin_bit_cast(uint32_t, x[k]) & 0x7fffffffu;
-            amax = ab > amax ? ab : amax;
-        }
-        const uint32_t other = (uint32_t)__shfl_xor((int)amax, 1);
-        amax = other > amax ? other : amax;
-        const int e = mx8_group_exp(amax);
-        const float inv = __builtin_bit_cast(float, mx8_pow2_bits(-e));
-        u32x4 c;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            float y[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) y[j] = __builtin_fminf(__builtin_fmaxf(x[4 * k + j] * inv, -448.0f), 448.0f);
-            int d = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-            d = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], d, true);
-            c[k] = (uint32_t)d;
-        }
-        if (active) store16<NT>(reinterpret_cast<u32x4 *>(stripe_ptr(a, a.n_ext, a.unit_shift, codes + el)), c);
-        if ((lane & 1u) == 0) sw[r * 32 + (lane >> 1)] = (uint8_t)(e + kMx8ScaleBias);
-    }
-    // the wave's own LDS bytes: written above, read below by other lanes of the same wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t ng = ne >> 5;  // scale bytes of this tile, 1..64
-    if (lane < 4 && lane * 16 < ng) {
-        const uint32_t nb = ng - lane * 16;
-        if (nb >= 16) {
-            store16<NT>(reinterpret_cast<u32x4 *>(stripe_ptr(a, a.n_ext, a.unit_shift, scales + lane * 16)),
-                        *reinterpret_cast<const u32x4 *>(sw + lane * 16));
-        } else {
-            for (uint32_t j = 0; j < nb; j++)
-                *stripe_ptr(a, a.n_ext, a.unit_shift, scales + lane * 16 + j) = (char)sw[lane * 16 + j];
-        }
-    }
-    // the next tile writes sw again: not before these reads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// One get tile: the reverse; local stores are nontemporal.
-template <bool BF16>
-__device__ __forceinline__ void get_tile(const XferBatchArgs &a, char *lin, uint64_t codes, uint64_t scales,
-                                         uint32_t ne, uint32_t lane) {
-#pragma unroll
-    for (uint32_t r = 0; r < 2; r++) {
-        const uint32_t el = r * kRoundElems + lane * 16;
-        if (el >= ne) continue;
-        const u32x4 c = __builtin_nontemporal_load(
-            reinterpret_cast<const u32x4 *>(stripe_ptr(a, a.n_ext, a.unit_shift, codes + el)));
-        const uint8_t sb = *reinterpret_cast<const uint8_t *>(stripe_ptr(a, a.n_ext, a.unit_shift, scales + (el >> 5)));
-        const int e = (int)sb - kMx8ScaleBias;
-        u32x4 o[2];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[k], false);
-            const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[k], true);
-            const uint32_t h0 = narrow16<BF16>(__builtin_ldexpf(lo[0], e)), h1 = narrow16<BF16>(__builtin_ldexpf(lo[1], e));
-            const uint32_t h2 = narrow16<BF16>(__builtin_ldexpf(hi[0], e)), h3 = narrow16<BF16>(__builtin_ldexpf(hi[1], e));
-            o[k >> 1][(k & 1) * 2] = (h0 & 0xffffu) | (h1 << 16);
-            o[k >> 1][(k & 1) * 2 + 1] = (h2 & 0xffffu) | (h3 << 16);
-        }
-        u32x4 *d = reinterpret_cast<u32x4 *>(lin + 2ull * el);
-        store16<true>(d, o[0]);
-        store16<true>(d + 1, o[1]);
-    }
-}
 
 template <bool PUT_NT>
 __global__ __launch_bounds__(kThreads) void xfer_quant_kernel(XferBatchArgs a) {

@@ -6,6 +6,7 @@
 // net.cpp      network-tier client (owners on other nodes)
 // batch.cpp    batched one-sided ops, stream interop, transfer plans (hipGraph)
 // quant.cpp    converting one-sided ops (ocm_copy_onesided_quant: MXFP8 records)
+// quant_strided.cpp  strided converting ops (ocm_copy_onesided_quant_strided: one MXFP8 record per row)
 // strided.cpp  strided one-sided ops (ocm_copy_onesided_strided: rows, one stride per side)
 // acc.cpp      one-sided accumulate (ocm_copy_onesided_accumulate: remote fp32 += scale * local)
 // libocm.cpp   the C ABI (oncillamem.h)

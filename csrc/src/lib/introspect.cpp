@@ -31,6 +31,15 @@ void ocm_x_acc_counters(uint64_t out[3]) {
     out[2] = c.bytes_acc;
 }
 
+// The strided converting counters, likewise: calls, ops, 16-bit source bytes, record bytes.
+void ocm_x_quant_strided_counters(uint64_t out[4]) {
+    const OpCounters &c = S().ctr;
+    out[0] = c.n_quant_strided;
+    out[1] = c.n_quant_strided_ops;
+    out[2] = c.bytes_quant_strided_src;
+    out[3] = c.bytes_quant_strided_wire;
+}
+
 // Raw 64-byte handle of extent i (tests: the network tier's capability checks).
 int ocm_x_extent_handle(ocm_alloc_t a, int i, uint8_t *out) {
     if (!a || !out || i < 0 || (size_t)i >= a->ext.size()) return -1;

@@ -1,10 +1,13 @@
-// What the four kinds of descriptor list share on the host (batches in batch.cpp,
-// converting ops in quant.cpp, strided ops in strided.cpp, accumulates in acc.cpp): how a
+// What the kinds of descriptor list share on the host (batches in batch.cpp, converting
+// ops in quant.cpp, strided ops in strided.cpp, strided converting ops in
+// quant_strided.cpp, accumulates in acc.cpp): how a
 // call is entered and accounted, how launch arguments are filled from the pair and the
 // plan (ocm/list.h), how a large list's descriptors and wave table are packed for the
 // device, and the upload, launch and completion of one list (run_list). A kind brings
 // its argument check, its descriptors, its plan and its launch function.
 #pragma once
+#include <functional>
+
 #include "internal.h"
 
 namespace ocmlib {
@@ -132,6 +135,12 @@ int run_list(lib_alloc *a, Args &args, const std::vector<Op> &v,
     if (n_launches) (*n_launches)++;
     return async ? async_done(a, st) : sync_stream();
 }
+
+// The host path of converting ops (quant.cpp): a CPU app, a host local half, the network
+// tier. Encodes or decodes the plain ops `next` yields (false: no more), in order, on this
+// thread and moves each record with xfer(). Converting lists yield their ops, strided
+// converting lists (quant_strided.cpp) one op per row.
+int quant_host(lib_alloc *a, const std::function<bool(ocm_quant_params *)> &next);
 
 // Copy absolute device ranges (op.lin_off = address) into dst's remote half, one launch.
 int batch_put_abs(lib_alloc *dst, std::vector<XferBatchOp> &v);

@@ -38,8 +38,9 @@ static int check_quant_ops(lib_alloc *a, const struct ocm_quant_params *ops, int
     return 0;
 }
 
-// Host local half: op by op, in order; a record is contiguous on the remote side.
-static int quant_host(lib_alloc *a, const struct ocm_quant_params *ops, int n_ops) {
+// Host local half: record by record, in the order `next` yields them; a record is
+// contiguous on the remote side.
+int ocmlib::quant_host(lib_alloc *a, const std::function<bool(ocm_quant_params *)> &next) {
     State &s = S();
     if (s.device >= 0) {
         // the CPU reads and writes the local half: after queued async ops and stream dependencies
@@ -48,8 +49,7 @@ static int quant_host(lib_alloc *a, const struct ocm_quant_params *ops, int n_op
         if (honor_dep(a, nullptr, true) != 0) return -1;
     }
     std::vector<uint8_t> rec;
-    for (int i = 0; i < n_ops; i++) {
-        const ocm_quant_params &p = ops[i];
+    for (ocm_quant_params p; next(&p);) {
         if (p.elems == 0) continue;
         uint16_t *loc = reinterpret_cast<uint16_t *>(static_cast<char *>(a->local) + p.local_offset);
         const size_t rbytes = mx8_record_bytes(p.elems);
@@ -68,7 +68,10 @@ static int quant_impl(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_o
     const int path = list_enter(kQuant, lk, a, ops, n_ops,
                                 [&] { return check_quant_ops(a, ops, n_ops, src, wire) != 0 ? -1 : *src != 0; });
     if (path <= PATH_NONE) return path;
-    if (path == PATH_HOST) return quant_host(a, ops, n_ops);
+    if (path == PATH_HOST) {
+        int i = 0;
+        return quant_host(a, [&](ocm_quant_params *p) { return i < n_ops ? (*p = ops[i++], true) : false; });
+    }
     DeviceGuard guard(S().device);
     std::vector<XferBatchOp> v((size_t)n_ops, XferBatchOp{});
     for (int i = 0; i < n_ops; i++) {

@@ -82,6 +82,21 @@ class OcmStridedParams(ctypes.Structure):
     ]
 
 
+class OcmQuantStridedParams(ctypes.Structure):
+    """struct ocm_quant_strided_params (56 bytes)."""
+
+    _fields_ = [
+        ("local_offset", ctypes.c_uint64),
+        ("remote_offset", ctypes.c_uint64),
+        ("row_elems", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("local_stride", ctypes.c_uint64),
+        ("remote_stride", ctypes.c_uint64),
+        ("op_flag", ctypes.c_int32),
+        ("dtype", ctypes.c_uint32),
+    ]
+
+
 class OcmAccParams(ctypes.Structure):
     """struct ocm_acc_params (32 bytes)."""
 
@@ -202,6 +217,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_copy_onesided_batch": (i32, [vp, ctypes.POINTER(OcmParams), i32, i32]),
             "ocm_quant_bytes": (ctypes.c_size_t, [u64]),
             "ocm_copy_onesided_quant": (i32, [vp, ctypes.POINTER(OcmQuantParams), i32, i32]),
+            "ocm_copy_onesided_quant_strided": (i32, [vp, ctypes.POINTER(OcmQuantStridedParams), i32, i32]),
             "ocm_copy_onesided_strided": (i32, [vp, ctypes.POINTER(OcmStridedParams), i32, i32]),
             "ocm_copy_onesided_accumulate": (i32, [vp, ctypes.POINTER(OcmAccParams), i32, i32]),
             "ocm_stream_wait": (i32, [vp, vp]),
@@ -228,6 +244,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_x_pattern": (ctypes.c_longlong, [vp, u64, u64, ctypes.c_uint32, i32]),
             "ocm_x_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_acc_counters": (None, [ctypes.POINTER(u64)]),
+            "ocm_x_quant_strided_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_stats": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_health": (None, [ctypes.POINTER(u64)]),
             "ocm_x_tick_stats": (ctypes.c_int, [ctypes.POINTER(u64)]),
@@ -300,6 +317,7 @@ OCM_ACC_F32 = 1
 OCM_ACC_BF16 = 2
 OCM_ACC_FP16 = 3
 ACC_COUNTER_KEYS = ["n_acc", "n_acc_ops", "bytes_acc"]
+QUANT_STRIDED_COUNTER_KEYS = ["n_quant_strided", "n_quant_strided_ops", "bytes_quant_strided_src", "bytes_quant_strided_wire"]
 
 
 class Plan:
@@ -426,6 +444,35 @@ def strided_ops(ops) -> BatchOps:
     b.keep = rec
     b.strided = True
     return b
+
+
+def quant_strided_ops(ops, dtype) -> BatchOps:
+    """Descriptor list for Allocation.quant_strided_batch from an (n, 7) integer array (or rows)
+    [op_flag, local_offset, remote_offset, row_elems, rows, local_stride, remote_stride], every
+    op with `dtype`, built once (no per-op Python objects)."""
+    import numpy as np
+
+    a = np.asarray(ops)
+    a = (a if a.dtype == np.uint64 else a.astype(np.int64)).reshape(-1, 7)
+    n = int(a.shape[0])
+    rec = np.zeros(max(1, n), dtype=np.dtype([("lo", "<u8"), ("ro", "<u8"), ("re", "<u8"), ("rows", "<u8"), ("ls", "<u8"),
+                                              ("rs", "<u8"), ("flag", "<i4"), ("dt", "<u4")]))
+    if n:
+        for col, name in enumerate(("flag", "lo", "ro", "re", "rows", "ls", "rs")):
+            rec[name][:n] = a[:, col]
+        rec["dt"][:n] = quant_dtype(dtype)
+    b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmQuantStridedParams)), n)
+    b.keep = rec
+    b.quant_strided = True
+    return b
+
+
+def quant_strided_counters() -> dict:
+    """This process's strided converting counters (ocm_x_quant_strided_counters): calls, ops,
+    16-bit source bytes, record bytes."""
+    out = (ctypes.c_uint64 * len(QUANT_STRIDED_COUNTER_KEYS))()
+    load().ocm_x_quant_strided_counters(out)
+    return dict(zip(QUANT_STRIDED_COUNTER_KEYS, [int(v) for v in out]))
 
 
 def acc_dtype(dtype) -> int:
@@ -894,6 +941,21 @@ class Allocation:
             raise TypeError("quant_batch takes a quant_ops list, not a batch_ops one")
         if self._c.lib.ocm_copy_onesided_quant(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_quant: " + last_error())
+
+    def quant_strided_batch(self, ops, dtype=None, async_: bool = False) -> None:
+        """Strided converting ops in one launch (ocm_copy_onesided_quant_strided): row r of an op
+        is the converting op (local_offset + r * local_stride, remote_offset + r * remote_stride,
+        row_elems), so every row has an MXFP8 record of its own. `ops`: an (n, 7) integer array
+        (or rows) [op_flag, local_offset, remote_offset, row_elems, rows, local_stride,
+        remote_stride] sharing `dtype`; or a prepared :func:`quant_strided_ops` list (dtype then
+        unused)."""
+        arr = ops if isinstance(ops, BatchOps) else quant_strided_ops(ops, dtype)
+        if not getattr(arr, "quant_strided", False):
+            raise TypeError("quant_strided_batch takes a quant_strided_ops list, not a batch_ops, quant_ops, "
+                            "strided_ops or acc_ops one")
+        if self._c.lib.ocm_copy_onesided_quant_strided(self.handle, arr.array, arr.n,
+                                                       OCM_BATCH_ASYNC if async_ else 0) != 0:
+            raise OcmError("ocm_copy_onesided_quant_strided: " + last_error())
 
     def accumulate_batch(self, ops, dtype=None, scale: float = 1.0, async_: bool = False) -> None:
         """One-sided accumulate in one launch (ocm_copy_onesided_accumulate): for every element of

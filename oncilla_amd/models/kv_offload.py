@@ -20,6 +20,13 @@ block_bytes, num_gpu_blocks * block_bytes apart; in the pool it is L * block_byt
 contiguous bytes, layer-major. Each swapped block is one strided op
 (ocm_copy_onesided_strided, rows = L) and the whole list still one launch.
 
+``layers=L`` with ``compress="mxfp8-rows"`` combines the two: a pool block is L MXFP8
+records side by side, layer-major, one per layer, each rounded up to 32 bytes. Each
+swapped block is one strided converting op (ocm_copy_onesided_quant_strided, rows = L,
+local stride num_gpu_blocks * block_bytes, remote stride the rounded record), the whole
+list one launch, and every layer comes back rounded to the format on its own.
+(``compress="mxfp8"`` keeps one record per block and cannot be layered.)
+
 Streams: swap_out waits for work already queued on torch's current stream (the
 kernels that wrote the cache). After an async swap_in, that stream waits for the
 copies, so later attention kernels see the blocks without a host sync.
@@ -71,20 +78,25 @@ class PagedKVOffload:
         self.layers = int(layers)
         if self.layers < 0:
             raise ValueError("layers must be 0 (one cache of whole blocks) or the number of per-layer caches")
-        if self.layers and compress is not None:
-            raise ValueError("layers > 0 cannot be combined with compress: converting ops are not strided")
+        if self.layers and compress == "mxfp8":
+            raise ValueError("layers > 0 cannot be combined with compress='mxfp8' (one record per block): "
+                             "use compress='mxfp8-rows', one record per layer")
+        if compress == "mxfp8-rows" and not self.layers:
+            raise ValueError("compress='mxfp8-rows' keeps one record per layer: it needs layers > 0 "
+                             "(a cache of whole blocks takes compress='mxfp8')")
         # bytes between pool blocks: the block itself, or its MXFP8 record rounded up to 32
         self.pool_block_bytes = self.block_bytes
         if compress is not None:
-            if compress != "mxfp8":
-                raise ValueError(f"unknown compression {compress!r} (None or 'mxfp8')")
+            if compress not in ("mxfp8", "mxfp8-rows"):
+                raise ValueError(f"unknown compression {compress!r} (None, 'mxfp8' or 'mxfp8-rows')")
             if self.dtype not in (torch.float16, torch.bfloat16):
-                raise ValueError("compress='mxfp8' needs float16 or bfloat16 blocks")
+                raise ValueError(f"compress={compress!r} needs float16 or bfloat16 blocks")
             if self.block_elems % 32 or self.block_bytes % 16:
-                raise ValueError("compress='mxfp8' needs a block element count that is a multiple of 32")
-            self.pool_block_bytes = (api.quant_bytes(self.block_elems) + 31) // 32 * 32
-        if self.layers:
-            self.pool_block_bytes = self.layers * self.block_bytes  # a block's layers side by side
+                raise ValueError(f"compress={compress!r} needs a block element count that is a multiple of 32")
+            self.record_bytes = (api.quant_bytes(self.block_elems) + 31) // 32 * 32
+            self.pool_block_bytes = self.record_bytes
+        if self.layers:  # a block's layers side by side: their bytes, or their records
+            self.pool_block_bytes = self.layers * self.pool_block_bytes
         lead = (self.layers, num_gpu_blocks) if self.layers else (num_gpu_blocks,)
         local_bytes = math.prod(lead) * self.block_bytes
         self.alloc = client.alloc(kind, local_bytes=local_bytes,
@@ -122,7 +134,25 @@ class PagedKVOffload:
                        axis=1)
         return api.strided_ops(ops)
 
+    def _quant_strided_ops(self, pairs, put: bool) -> api.BatchOps:
+        # One op per block: rows = layers, a cache apart on the GPU, one record per layer side by
+        # side in the pool.
+        a = np.asarray(pairs if isinstance(pairs, np.ndarray) else list(pairs), dtype=np.int64).reshape(-1, 2)
+        g, p = (a[:, 0], a[:, 1]) if put else (a[:, 1], a[:, 0])  # (gpu block, pool block)
+        if len(a) and ((g < 0).any() or (g >= self.num_gpu_blocks).any() or (p < 0).any()
+                       or (p >= self.num_pool_blocks).any()):
+            raise IndexError("block out of range")
+        if len(a) and len(np.unique(a[:, 1])) != len(a):
+            raise ValueError("compressed swaps take one op per block: a destination block is named twice")
+        bb = self.block_bytes
+        ops = np.stack([np.full_like(g, 1 if put else 0), g * bb, p * self.pool_block_bytes,
+                        np.full_like(g, self.block_elems), np.full_like(g, self.layers),
+                        np.full_like(g, self.num_gpu_blocks * bb), np.full_like(g, self.record_bytes)], axis=1)
+        return api.quant_strided_ops(ops, self.dtype)
+
     def _ops(self, pairs, put: bool) -> api.BatchOps:
+        if self.compress == "mxfp8-rows":
+            return self._quant_strided_ops(pairs, put)
         if self.compress:
             return self._quant_ops(pairs, put)
         if self.layers:
@@ -138,7 +168,9 @@ class PagedKVOffload:
         return api.batch_ops(ops)
 
     def _run(self, ops: api.BatchOps, async_: bool) -> None:
-        if self.compress:
+        if self.compress == "mxfp8-rows":
+            self.alloc.quant_strided_batch(ops, async_=async_)
+        elif self.compress:
             self.alloc.quant_batch(ops, async_=async_)
         elif self.layers:
             self.alloc.strided_batch(ops, async_=async_)

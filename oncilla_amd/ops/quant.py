@@ -68,3 +68,16 @@ def mx8_record_reference(x):
 
     codes, scales = mx8_encode_reference(x)
     return torch.cat([codes, scales])
+
+
+def mx8_rows_reference(x2d):
+    """The records of a [rows, row_elems] tensor as ``ocm_copy_onesided_quant_strided`` writes
+    them, one per row (each row's codes, then its scale bytes): a uint8 tensor
+    [rows, row_elems + row_elems / 32]."""
+    import torch
+
+    if x2d.dim() != 2:
+        raise ValueError("mx8_rows_reference takes a [rows, row_elems] tensor")
+    if x2d.shape[0] == 0:
+        return torch.zeros((0, x2d.shape[1] + x2d.shape[1] // GROUP), dtype=torch.uint8)
+    return torch.stack([mx8_record_reference(row) for row in x2d])
