@@ -1,6 +1,6 @@
 // Strided converting one-sided ops (ocm_copy_onesided_quant_strided): `rows` rows of
-// `row_elems` 16-bit elements on the local side, one MXFP8 record (ocm/mx8.h: the row's
-// codes, then its scale bytes) per row on the remote side, one stride per side. By
+// `row_elems` 16-bit elements on the local side, one MXFP8 or MXFP4 record (ocm/mx8.h,
+// ocm/mx4.h: the row's codes, then its scale bytes) per row on the remote side, one stride per side. By
 // definition the call is the ocm_copy_onesided_quant list with one op per row, so a
 // plain converting get can read one row of what a strided put wrote. One launch serves
 // a whole list, planned as every descriptor list is (ocm/list.h); one descriptor per op
@@ -20,7 +20,7 @@
 #include <cstdio>
 
 #include "ocm/list.h"
-#include "ocm/mx8.h"
+#include "ocm/mx4.h"
 #include "oncillamem.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -41,7 +41,7 @@ struct XferQuantStridedOp {
     uint32_t rows;
     uint32_t tiles_per_row;  // ceil(row_elems / kQuantTileElems)
     uint32_t put;            // 1: encode lin -> striped, 0: decode striped -> lin
-    uint32_t dtype;          // enum ocm_quant_dtype
+    uint32_t dtype;          // enum ocm_quant_dtype | enum ocm_quant_format
     uint32_t pad;
 };
 static_assert(sizeof(XferQuantStridedOp) == 64, "strided converting op layout");
@@ -74,16 +74,17 @@ OCM_QS_HD inline void quant_strided_locate(const XferQuantStridedOp &op, uint64_
 }
 
 // Piece k of row `row`: exactly the tile (k) of the plain converting op
-// (lin_off + row * lin_stride, rem_off + row * rem_stride, row_elems).
-OCM_QS_HD inline QuantTileLoc quant_strided_tile(const XferQuantStridedOp &op, uint64_t row, uint32_t k) {
+// (lin_off + row * lin_stride, rem_off + row * rem_stride, row_elems). code_shift: log2 of
+// the elements a code byte of the op's format holds (quant_code_shift).
+OCM_QS_HD inline QuantTileLoc quant_strided_tile(const XferQuantStridedOp &op, uint64_t row, uint32_t k, uint32_t code_shift) {
     const uint32_t e0 = k << kQuantTileShift;  // row_elems < 2^31
     const uint32_t left = op.row_elems - e0;
     const uint64_t rec = op.rem_off + row * op.rem_stride;
     QuantTileLoc q;
     q.ne = left < kQuantTileElems ? left : kQuantTileElems;
     q.lin_off = op.lin_off + row * op.lin_stride + 2ull * e0;
-    q.codes = rec + e0;
-    q.scales = rec + op.row_elems + (e0 >> 5);
+    q.codes = rec + (e0 >> code_shift);
+    q.scales = rec + (op.row_elems >> code_shift) + (e0 >> 5);
     return q;
 }
 
@@ -95,10 +96,7 @@ OCM_QS_HD inline QuantTileLoc quant_strided_tile(const XferQuantStridedOp &op, u
 inline int quant_strided_check_op(const struct ocm_quant_strided_params &p, uint64_t local_bytes, uint64_t remote_bytes,
                                   uint64_t *src, uint64_t *wire, char *why, size_t why_len) {
     *src = *wire = 0;
-    if (p.dtype != OCM_QUANT_BF16 && p.dtype != OCM_QUANT_FP16) {
-        std::snprintf(why, why_len, "unknown element type %u", p.dtype);
-        return -1;
-    }
+    if (quant_check_dtype(p.dtype, why, why_len) != 0) return -1;
     if (p.row_elems % kMx8Group != 0 || p.row_elems >= (1ull << 31)) {
         std::snprintf(why, why_len, "rows of %llu elements (a multiple of 32 below 2^31 is needed)",
                       (unsigned long long)p.row_elems);
@@ -113,7 +111,7 @@ inline int quant_strided_check_op(const struct ocm_quant_strided_params &p, uint
         const char *side;
         uint64_t off, stride, size, row_bytes, align;
     } sides[2] = {{"local", p.local_offset, p.local_stride, local_bytes, 2 * p.row_elems, 16},
-                  {"remote", p.remote_offset, p.remote_stride, remote_bytes, mx8_record_bytes(p.row_elems), 32}};
+                  {"remote", p.remote_offset, p.remote_stride, remote_bytes, quant_record_bytes(p.row_elems, p.dtype), 32}};
     for (const auto &s : sides) {
         if (s.off % s.align != 0) {
             std::snprintf(why, why_len, "%s offset %llu is not a multiple of %llu", s.side, (unsigned long long)s.off,

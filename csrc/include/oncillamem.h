@@ -160,17 +160,29 @@ int ocm_copy_onesided_batch(ocm_alloc_t a, const struct ocm_params *ops, int n_o
  * elems < 2^31, local_offset % 16 == 0, remote_offset % 32 == 0, both ranges inside
  * their halves. Ops of one call run concurrently, puts and gets mixed, as ONE gfx950
  * launch when the local half is device memory; flags and ordering as for
- * ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait, ocm_stream_wait/signal). */
+ * ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait, ocm_stream_wait/signal).
+ *
+ * The record format is chosen per op: dtype = element type | record format, the element
+ * type (enum ocm_quant_dtype) in the low byte and the format (enum ocm_quant_format) in
+ * bits 8 to 15; any other bit and any unknown format is rejected. A bare element type is
+ * MXFP8, as above. OCM_QUANT_MXFP4 records take 17/64 of the bytes: elems / 2 code bytes
+ * of OCP E2M1 codes (element 2i in the low nibble of byte i, element 2i + 1 in the high
+ * one), then elems / 32 scale bytes, with 2^e the smallest scale with max|x| * 2^-e <= 6.
+ * The constraints per op are the same. Ops of both formats may be mixed in one list. */
 enum ocm_quant_dtype { OCM_QUANT_BF16 = 1, OCM_QUANT_FP16 = 2 };
+enum ocm_quant_format { OCM_QUANT_MXFP8 = 0, OCM_QUANT_MXFP4 = 0x100 };
 struct ocm_quant_params {
     uint64_t local_offset;  /* bytes into the local half */
     uint64_t remote_offset; /* first byte of the record in the remote half */
     uint64_t elems;         /* 16-bit elements */
     int32_t  op_flag;       /* 1 = put (encode), 0 = get (decode) */
-    uint32_t dtype;         /* enum ocm_quant_dtype */
+    uint32_t dtype;         /* enum ocm_quant_dtype | enum ocm_quant_format */
 };
-/* Bytes of the record of `elems` elements: elems + elems / 32. */
+/* Bytes of the MXFP8 record of `elems` elements: elems + elems / 32. */
 size_t ocm_quant_bytes(uint64_t elems);
+/* Bytes of the record of `elems` elements in `format` (enum ocm_quant_format): MXFP8 as
+ * ocm_quant_bytes, MXFP4 elems / 2 + elems / 32; 0 for an unknown format. */
+size_t ocm_quant_bytes_fmt(uint64_t elems, uint32_t format);
 int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags);
 /* Strided converting copies (layer-major KV caches): by definition the
  * ocm_copy_onesided_quant list with one op per row. Row r of an op is the converting op
@@ -181,8 +193,9 @@ int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, i
  * gets mixed, as ONE gfx950 launch when the local half is device memory. Per op: dtype
  * known, row_elems % 32 == 0 and row_elems < 2^31, rows < 2^32, local_offset and
  * local_stride multiples of 16, remote_offset and remote_stride multiples of 32, with
- * rows > 1 local_stride >= 2 * row_elems and remote_stride >= row_elems + row_elems / 32,
- * and the last row's end inside its half on both sides; an op with rows == 0 or
+ * rows > 1 local_stride >= 2 * row_elems and remote_stride >= the row's record bytes
+ * (ocm_quant_bytes_fmt: row_elems + row_elems / 32, or row_elems / 2 + row_elems / 32
+ * for OCM_QUANT_MXFP4), and the last row's end inside its half on both sides; an op with rows == 0 or
  * row_elems == 0 does nothing. flags and ordering as for ocm_copy_onesided_batch
  * (OCM_BATCH_ASYNC, ocm_wait, ocm_stream_wait/signal). */
 struct ocm_quant_strided_params {
@@ -193,7 +206,7 @@ struct ocm_quant_strided_params {
     uint64_t local_stride;   /* bytes from one row's start to the next, local side */
     uint64_t remote_stride;  /* bytes from one row's record to the next, remote side */
     int32_t  op_flag;        /* 1 = put (encode), 0 = get (decode) */
-    uint32_t dtype;          /* enum ocm_quant_dtype */
+    uint32_t dtype;          /* enum ocm_quant_dtype | enum ocm_quant_format */
 };
 int ocm_copy_onesided_quant_strided(ocm_alloc_t a, const struct ocm_quant_strided_params *ops, int n_ops, int flags);
 /* Strided one-sided copies (2-D put / get): row r of an op moves row_bytes bytes between

@@ -1,6 +1,8 @@
-// Converting one-sided ops: bf16 / fp16 <-> MXFP8 records (ocm/mx8.h) as the bytes
-// cross to the remote half, one launch per list; see ocm/quant.h for the plan. The
-// tile bodies (put_tile, get_tile) are in quant_tile.h, shared with xfer_quant_strided.hip.
+// Converting one-sided ops: bf16 / fp16 <-> MXFP8 or MXFP4 records (ocm/mx8.h, ocm/mx4.h)
+// as the bytes cross to the remote half, one launch per list; see ocm/quant.h for the
+// plan. The tile bodies (put_tile, get_tile and their _mx4 forms) are in quant_tile.h,
+// shared with xfer_quant_strided.hip; an op's format, like its element type, is a
+// wave-uniform branch. What follows describes the MXFP8 tile; quant_tile.h has both.
 //
 // A wave-tile is 2048 elements, done in two rounds of 1024. In a round lane l owns
 // elements [16 l, 16 l + 16): two 16-byte vectors of source, one 16-byte vector of
@@ -14,7 +16,7 @@
 // vector goes byte by byte.
 #include <hip/hip_runtime.h>
 
-#include "ocm/mx8.h"
+#include "ocm/mx4.h"
 #include "ocm/quant.h"
 #include "quant_tile.h"
 #include "xfer_copy.h"
@@ -43,9 +45,22 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_kernel(XferBatchArgs a) {
         const uint32_t left = (uint32_t)op.len - e0;
         const uint32_t ne = left < kQuantTileElems ? left : kQuantTileElems;
         char *lin = a.lin + op.lin_off + 2ull * e0;
-        const uint64_t codes = op.rem_off + e0, scales = op.rem_off + op.len + (e0 >> 5);
-        const bool bf16 = op.pad == kMx8Bf16;
-        if (op.put) {
+        const uint32_t cs = quant_code_shift(op.pad);  // elements per code byte, log2
+        const uint64_t codes = op.rem_off + (e0 >> cs), scales = op.rem_off + (op.len >> cs) + (e0 >> 5);
+        const bool bf16 = (op.pad & kQuantElemMask) == kMx8Bf16;
+        if (cs) {
+            if (op.put) {
+                if (bf16)
+                    put_tile_mx4<true, PUT_NT>(a, lin, codes, scales, ne, lane, scale_lds[wl]);
+                else
+                    put_tile_mx4<false, PUT_NT>(a, lin, codes, scales, ne, lane, scale_lds[wl]);
+            } else {
+                if (bf16)
+                    get_tile_mx4<true>(a, lin, codes, scales, ne, lane);
+                else
+                    get_tile_mx4<false>(a, lin, codes, scales, ne, lane);
+            }
+        } else if (op.put) {
             if (bf16)
                 put_tile<true, PUT_NT>(a, lin, codes, scales, ne, lane, scale_lds[wl]);
             else

@@ -1,4 +1,4 @@
-// Strided converting one-sided ops: rows of 16-bit elements <-> one MXFP8 record per
+// Strided converting one-sided ops: rows of 16-bit elements <-> one MXFP8 or MXFP4 record per
 // row, one launch per list; see ocm/quant_strided.h for the descriptor, the
 // row-relative tile rule and the plan the host makes.
 //
@@ -11,7 +11,7 @@
 // kernel arguments for short lists.
 #include <hip/hip_runtime.h>
 
-#include "ocm/mx8.h"
+#include "ocm/mx4.h"
 #include "ocm/quant.h"
 #include "ocm/quant_strided.h"
 #include "quant_tile.h"
@@ -69,10 +69,23 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_strided_kernel(XferQuantS
             row = uniform64(row);
             k = uniform32(k);
         }
-        const QuantTileLoc q = quant_strided_tile(op, row, k);
+        const uint32_t cs = quant_code_shift(op.dtype);  // elements per code byte, log2
+        const QuantTileLoc q = quant_strided_tile(op, row, k, cs);
         char *lin = a.lin + q.lin_off;
-        const bool bf16 = op.dtype == kMx8Bf16;
-        if (op.put) {
+        const bool bf16 = (op.dtype & kQuantElemMask) == kMx8Bf16;
+        if (cs) {
+            if (op.put) {
+                if (bf16)
+                    put_tile_mx4<true, PUT_NT>(a, lin, q.codes, q.scales, q.ne, lane, scale_lds[wl]);
+                else
+                    put_tile_mx4<false, PUT_NT>(a, lin, q.codes, q.scales, q.ne, lane, scale_lds[wl]);
+            } else {
+                if (bf16)
+                    get_tile_mx4<true>(a, lin, q.codes, q.scales, q.ne, lane);
+                else
+                    get_tile_mx4<false>(a, lin, q.codes, q.scales, q.ne, lane);
+            }
+        } else if (op.put) {
             if (bf16)
                 put_tile<true, PUT_NT>(a, lin, q.codes, q.scales, q.ne, lane, scale_lds[wl]);
             else

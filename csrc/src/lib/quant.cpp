@@ -1,10 +1,11 @@
 // libocm converting one-sided ops (ocm_copy_onesided_quant): 16-bit elements in
-// the local half, MXFP8 records (ocm/mx8.h) in the remote half. A device local
+// the local half, MXFP8 or MXFP4 records (ocm/mx8.h, ocm/mx4.h; the op's dtype word
+// says which) in the remote half. A device local
 // half takes one kernel launch per list (ocm/quant.h), ordered like a batch; a
 // host local half (a CPU app, OCM_REMOTE_RDMA / _RMA pairs, the network tier)
 // encodes and decodes on this thread and moves each record with xfer().
 #include "lists.h"
-#include "ocm/mx8.h"
+#include "ocm/mx4.h"
 
 using namespace ocm;
 using namespace ocmlib;
@@ -15,8 +16,8 @@ static const ListNames kQuant = {"ocm_copy_onesided_quant", "converting one-side
 static int check_quant_ops(lib_alloc *a, const struct ocm_quant_params *ops, int n_ops, uint64_t *src, uint64_t *wire) {
     for (int i = 0; i < n_ops; i++) {
         const ocm_quant_params &p = ops[i];
-        if (p.dtype != OCM_QUANT_BF16 && p.dtype != OCM_QUANT_FP16)
-            OCM_FAIL(-1, "quant op %d: unknown element type %u", i, p.dtype);
+        char why[96];
+        if (quant_check_dtype(p.dtype, why, sizeof(why)) != 0) OCM_FAIL(-1, "quant op %d: %s", i, why);
         if (p.elems % kMx8Group != 0 || p.elems >= (1ull << 31))
             OCM_FAIL(-1, "quant op %d: %llu elements (a multiple of 32 below 2^31 is needed)", i,
                      (unsigned long long)p.elems);
@@ -25,7 +26,7 @@ static int check_quant_ops(lib_alloc *a, const struct ocm_quant_params *ops, int
         if (p.remote_offset % 32 != 0)
             OCM_FAIL(-1, "quant op %d: remote offset %llu is not a multiple of 32", i,
                      (unsigned long long)p.remote_offset);
-        const uint64_t lbytes = 2 * p.elems, rbytes = mx8_record_bytes(p.elems);
+        const uint64_t lbytes = 2 * p.elems, rbytes = quant_record_bytes(p.elems, p.dtype);
         if (p.local_offset > a->local_bytes || lbytes > a->local_bytes - p.local_offset)
             OCM_FAIL(-1, "quant op %d: local range [%llu,+%llu) exceeds %zu bytes", i,
                      (unsigned long long)p.local_offset, (unsigned long long)lbytes, a->local_bytes);
@@ -52,12 +53,12 @@ int ocmlib::quant_host(lib_alloc *a, const std::function<bool(ocm_quant_params *
     for (ocm_quant_params p; next(&p);) {
         if (p.elems == 0) continue;
         uint16_t *loc = reinterpret_cast<uint16_t *>(static_cast<char *>(a->local) + p.local_offset);
-        const size_t rbytes = mx8_record_bytes(p.elems);
+        const size_t rbytes = quant_record_bytes(p.elems, p.dtype);
         rec.resize(rbytes);
-        if (p.op_flag != 0) mx8_encode(loc, p.elems, p.dtype, rec.data());
+        if (p.op_flag != 0) quant_encode(loc, p.elems, p.dtype, rec.data());
         if (xfer(a, p.op_flag != 0, reinterpret_cast<char *>(rec.data()), LOC_HOST, p.remote_offset, rbytes, false) != 0)
             return -1;
-        if (p.op_flag == 0) mx8_decode(rec.data(), p.elems, p.dtype, loc);
+        if (p.op_flag == 0) quant_decode(rec.data(), p.elems, p.dtype, loc);
     }
     return 0;
 }
@@ -89,6 +90,10 @@ static int quant_impl(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_o
 extern "C" {
 
 size_t ocm_quant_bytes(uint64_t elems) { return mx8_record_bytes(elems); }
+
+size_t ocm_quant_bytes_fmt(uint64_t elems, uint32_t format) {
+    return format == OCM_QUANT_MXFP8 || format == OCM_QUANT_MXFP4 ? quant_record_bytes(elems, format) : 0;
+}
 
 int ocm_copy_onesided_quant(ocm_alloc_t a, const struct ocm_quant_params *ops, int n_ops, int flags) {
     uint64_t src = 0, wire = 0;

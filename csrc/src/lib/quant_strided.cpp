@@ -1,5 +1,5 @@
 // libocm strided converting ops (ocm_copy_onesided_quant_strided): rows of 16-bit
-// elements in the local half, one MXFP8 record per row in the remote half, one stride
+// elements in the local half, one MXFP8 or MXFP4 record per row in the remote half, one stride
 // per side (ocm/quant_strided.h). A device local half takes one kernel launch per list,
 // uploaded and ordered like a batch (run_list); a host local half (a CPU app,
 // OCM_REMOTE_RDMA / _RMA pairs, the network tier) goes op by op, row by row, in order,

@@ -64,7 +64,7 @@ void check_op(XferQuantStridedOp op, uint64_t *tiles_seen) {
         quant_strided_locate(op, t, &row, &k);
         CHECK(row == t / op.tiles_per_row && k == t % op.tiles_per_row, "tile %llu located at row %llu piece %u", (ull)t,
               (ull)row, k);
-        const QuantTileLoc q = quant_strided_tile(op, row, k);
+        const QuantTileLoc q = quant_strided_tile(op, row, k, 0);  // MXFP8: one code byte per element
         (*tiles_seen)++;
         // the plain op of this row, cut as xfer_quant_kernel cuts it
         const uint64_t lin_off = op.lin_off + row * op.lin_stride, rem_off = op.rem_off + row * op.rem_stride;

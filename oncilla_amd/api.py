@@ -216,6 +216,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_wait": (i32, [vp]),
             "ocm_copy_onesided_batch": (i32, [vp, ctypes.POINTER(OcmParams), i32, i32]),
             "ocm_quant_bytes": (ctypes.c_size_t, [u64]),
+            "ocm_quant_bytes_fmt": (ctypes.c_size_t, [u64, ctypes.c_uint32]),
             "ocm_copy_onesided_quant": (i32, [vp, ctypes.POINTER(OcmQuantParams), i32, i32]),
             "ocm_copy_onesided_quant_strided": (i32, [vp, ctypes.POINTER(OcmQuantStridedParams), i32, i32]),
             "ocm_copy_onesided_strided": (i32, [vp, ctypes.POINTER(OcmStridedParams), i32, i32]),
@@ -313,6 +314,8 @@ COUNTER_KEYS = ["n_put", "n_get", "bytes_put", "bytes_get", "n_alloc", "n_free",
 OCM_BATCH_ASYNC = 1
 OCM_QUANT_BF16 = 1
 OCM_QUANT_FP16 = 2
+OCM_QUANT_MXFP8 = 0  # enum ocm_quant_format: bits 8 to 15 of a converting op's dtype word
+OCM_QUANT_MXFP4 = 0x100
 OCM_ACC_F32 = 1
 OCM_ACC_BF16 = 2
 OCM_ACC_FP16 = 3
@@ -392,9 +395,29 @@ def batch_ops(ops) -> BatchOps:
     return BatchOps(arr, len(ops))
 
 
-def quant_bytes(elems: int) -> int:
-    """Bytes of the MXFP8 record of `elems` 16-bit elements: elems + elems / 32 (ocm_quant_bytes)."""
-    return int(load().ocm_quant_bytes(int(elems)))
+def quant_format(format) -> int:
+    """enum ocm_quant_format of "mxfp8" / "mxfp4", or of the enum value itself."""
+    if isinstance(format, int):
+        return format
+    try:
+        return {"mxfp8": OCM_QUANT_MXFP8, "mxfp4": OCM_QUANT_MXFP4}[format]
+    except (KeyError, TypeError):
+        raise ValueError(f"converting ops take the record format 'mxfp8' or 'mxfp4', not {format!r}") from None
+
+
+def _quant_formats(format):
+    # one format for the whole list, or one per op
+    import numpy as np
+
+    if isinstance(format, (str, int)):
+        return quant_format(format)
+    return np.array([quant_format(f) for f in format], dtype=np.uint32)
+
+
+def quant_bytes(elems: int, format="mxfp8") -> int:
+    """Bytes of the record of `elems` 16-bit elements (ocm_quant_bytes_fmt): elems + elems / 32 as
+    MXFP8, elems / 2 + elems / 32 as MXFP4."""
+    return int(load().ocm_quant_bytes_fmt(int(elems), quant_format(format)))
 
 
 def quant_dtype(dtype) -> int:
@@ -409,9 +432,10 @@ def quant_dtype(dtype) -> int:
         raise ValueError(f"converting ops take bfloat16 or float16 elements, not {dtype}") from None
 
 
-def quant_ops(ops, dtype) -> BatchOps:
+def quant_ops(ops, dtype, format="mxfp8") -> BatchOps:
     """Descriptor list for Allocation.quant_batch from an (n, 4) integer array (or rows)
-    [op_flag, local_offset, remote_offset, elems], built once (no per-op Python objects)."""
+    [op_flag, local_offset, remote_offset, elems], built once (no per-op Python objects).
+    format: "mxfp8" or "mxfp4" for every op, or a sequence with one of them per op."""
     import numpy as np
 
     a = np.asarray(ops, dtype=np.int64).reshape(-1, 4)
@@ -419,7 +443,7 @@ def quant_ops(ops, dtype) -> BatchOps:
     rec = np.zeros(max(1, n), dtype=np.dtype([("lo", "<u8"), ("ro", "<u8"), ("el", "<u8"), ("flag", "<i4"), ("dt", "<u4")]))
     if n:
         rec["lo"][:n], rec["ro"][:n], rec["el"][:n], rec["flag"][:n] = a[:, 1], a[:, 2], a[:, 3], a[:, 0]
-        rec["dt"][:n] = quant_dtype(dtype)
+        rec["dt"][:n] = quant_dtype(dtype) | _quant_formats(format)
     b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmQuantParams)), n)
     b.keep = rec
     b.quant = True
@@ -446,10 +470,11 @@ def strided_ops(ops) -> BatchOps:
     return b
 
 
-def quant_strided_ops(ops, dtype) -> BatchOps:
+def quant_strided_ops(ops, dtype, format="mxfp8") -> BatchOps:
     """Descriptor list for Allocation.quant_strided_batch from an (n, 7) integer array (or rows)
     [op_flag, local_offset, remote_offset, row_elems, rows, local_stride, remote_stride], every
-    op with `dtype`, built once (no per-op Python objects)."""
+    op with `dtype`, built once (no per-op Python objects). format: "mxfp8" or "mxfp4" for
+    every op, or a sequence with one of them per op."""
     import numpy as np
 
     a = np.asarray(ops)
@@ -460,7 +485,7 @@ def quant_strided_ops(ops, dtype) -> BatchOps:
     if n:
         for col, name in enumerate(("flag", "lo", "ro", "re", "rows", "ls", "rs")):
             rec[name][:n] = a[:, col]
-        rec["dt"][:n] = quant_dtype(dtype)
+        rec["dt"][:n] = quant_dtype(dtype) | _quant_formats(format)
     b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmQuantStridedParams)), n)
     b.keep = rec
     b.quant_strided = True
@@ -929,27 +954,29 @@ class Allocation:
         if self._c.lib.ocm_copy_onesided_batch(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_batch: " + last_error())
 
-    def quant_batch(self, ops, dtype=None, async_: bool = False) -> None:
+    def quant_batch(self, ops, dtype=None, async_: bool = False, format="mxfp8") -> None:
         """Converting one-sided ops in one launch (ocm_copy_onesided_quant): 16-bit elements of
-        `dtype` (torch.bfloat16 / torch.float16) in the local half, MXFP8 records in the remote half.
+        `dtype` (torch.bfloat16 / torch.float16) in the local half, records of `format` ("mxfp8"
+        or "mxfp4") in the remote half.
 
         ops: an (n, 4) integer array [op_flag, local_offset, remote_offset, elems] with op_flag
-        1 = put (encode), 0 = get (decode); or a prepared :func:`quant_ops` list (dtype then unused).
+        1 = put (encode), 0 = get (decode); or a prepared :func:`quant_ops` list (dtype and format
+        then unused).
         """
-        arr = ops if isinstance(ops, BatchOps) else quant_ops(ops, dtype)
+        arr = ops if isinstance(ops, BatchOps) else quant_ops(ops, dtype, format)
         if not getattr(arr, "quant", False):
             raise TypeError("quant_batch takes a quant_ops list, not a batch_ops one")
         if self._c.lib.ocm_copy_onesided_quant(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_quant: " + last_error())
 
-    def quant_strided_batch(self, ops, dtype=None, async_: bool = False) -> None:
+    def quant_strided_batch(self, ops, dtype=None, async_: bool = False, format="mxfp8") -> None:
         """Strided converting ops in one launch (ocm_copy_onesided_quant_strided): row r of an op
         is the converting op (local_offset + r * local_stride, remote_offset + r * remote_stride,
-        row_elems), so every row has an MXFP8 record of its own. `ops`: an (n, 7) integer array
-        (or rows) [op_flag, local_offset, remote_offset, row_elems, rows, local_stride,
-        remote_stride] sharing `dtype`; or a prepared :func:`quant_strided_ops` list (dtype then
-        unused)."""
-        arr = ops if isinstance(ops, BatchOps) else quant_strided_ops(ops, dtype)
+        row_elems), so every row has a record of its own, of `format` ("mxfp8" or "mxfp4"). `ops`:
+        an (n, 7) integer array (or rows) [op_flag, local_offset, remote_offset, row_elems, rows,
+        local_stride, remote_stride] sharing `dtype`; or a prepared :func:`quant_strided_ops` list
+        (dtype and format then unused)."""
+        arr = ops if isinstance(ops, BatchOps) else quant_strided_ops(ops, dtype, format)
         if not getattr(arr, "quant_strided", False):
             raise TypeError("quant_strided_batch takes a quant_strided_ops list, not a batch_ops, quant_ops, "
                             "strided_ops or acc_ops one")

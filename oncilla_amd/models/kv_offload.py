@@ -27,6 +27,10 @@ local stride num_gpu_blocks * block_bytes, remote stride the rounded record), th
 list one launch, and every layer comes back rounded to the format on its own.
 (``compress="mxfp8"`` keeps one record per block and cannot be layered.)
 
+``compress="mxfp4"`` and ``compress="mxfp4-rows"`` are the same two layouts with MXFP4
+records (E2M1 codes, two to a byte, ``oncilla_amd.ops.mx4_encode_reference``): 17/64 of
+the bytes, so a pool of the same size holds 1.94 times the blocks of an MXFP8 one.
+
 Streams: swap_out waits for work already queued on torch's current stream (the
 kernels that wrote the cache). After an async swap_in, that stream waits for the
 copies, so later attention kernels see the blocks without a host sync.
@@ -78,22 +82,24 @@ class PagedKVOffload:
         self.layers = int(layers)
         if self.layers < 0:
             raise ValueError("layers must be 0 (one cache of whole blocks) or the number of per-layer caches")
-        if self.layers and compress == "mxfp8":
-            raise ValueError("layers > 0 cannot be combined with compress='mxfp8' (one record per block): "
-                             "use compress='mxfp8-rows', one record per layer")
-        if compress == "mxfp8-rows" and not self.layers:
-            raise ValueError("compress='mxfp8-rows' keeps one record per layer: it needs layers > 0 "
-                             "(a cache of whole blocks takes compress='mxfp8')")
-        # bytes between pool blocks: the block itself, or its MXFP8 record rounded up to 32
+        if self.layers and compress in ("mxfp8", "mxfp4"):
+            raise ValueError(f"layers > 0 cannot be combined with compress='{compress}' (one record per block): "
+                             f"use compress='{compress}-rows', one record per layer")
+        if compress in ("mxfp8-rows", "mxfp4-rows") and not self.layers:
+            raise ValueError(f"compress='{compress}' keeps one record per layer: it needs layers > 0 "
+                             f"(a cache of whole blocks takes compress='{compress[:5]}')")
+        # bytes between pool blocks: the block itself, or its record rounded up to 32
         self.pool_block_bytes = self.block_bytes
         if compress is not None:
-            if compress not in ("mxfp8", "mxfp8-rows"):
-                raise ValueError(f"unknown compression {compress!r} (None, 'mxfp8' or 'mxfp8-rows')")
+            if compress not in ("mxfp8", "mxfp8-rows", "mxfp4", "mxfp4-rows"):
+                raise ValueError(f"unknown compression {compress!r} (None, 'mxfp8', 'mxfp8-rows', 'mxfp4' or "
+                                 "'mxfp4-rows')")
+            self.format = compress[:5]  # the record format: "mxfp8" or "mxfp4"
             if self.dtype not in (torch.float16, torch.bfloat16):
                 raise ValueError(f"compress={compress!r} needs float16 or bfloat16 blocks")
             if self.block_elems % 32 or self.block_bytes % 16:
                 raise ValueError(f"compress={compress!r} needs a block element count that is a multiple of 32")
-            self.record_bytes = (api.quant_bytes(self.block_elems) + 31) // 32 * 32
+            self.record_bytes = (api.quant_bytes(self.block_elems, self.format) + 31) // 32 * 32
             self.pool_block_bytes = self.record_bytes
         if self.layers:  # a block's layers side by side: their bytes, or their records
             self.pool_block_bytes = self.layers * self.pool_block_bytes
@@ -117,7 +123,7 @@ class PagedKVOffload:
                         np.full_like(g, self.block_elems)], axis=1)
         if len(a) and len(np.unique(a[:, 1])) != len(a):
             raise ValueError("compressed swaps take one op per block: a destination block is named twice")
-        return api.quant_ops(ops, self.dtype)
+        return api.quant_ops(ops, self.dtype, self.format)
 
     def _strided_ops(self, pairs, put: bool) -> api.BatchOps:
         # One op per block: rows = layers, a cache apart on the GPU, side by side in the pool.
@@ -148,10 +154,10 @@ class PagedKVOffload:
         ops = np.stack([np.full_like(g, 1 if put else 0), g * bb, p * self.pool_block_bytes,
                         np.full_like(g, self.block_elems), np.full_like(g, self.layers),
                         np.full_like(g, self.num_gpu_blocks * bb), np.full_like(g, self.record_bytes)], axis=1)
-        return api.quant_strided_ops(ops, self.dtype)
+        return api.quant_strided_ops(ops, self.dtype, self.format)
 
     def _ops(self, pairs, put: bool) -> api.BatchOps:
-        if self.compress == "mxfp8-rows":
+        if self.compress and self.compress.endswith("-rows"):
             return self._quant_strided_ops(pairs, put)
         if self.compress:
             return self._quant_ops(pairs, put)
@@ -168,7 +174,7 @@ class PagedKVOffload:
         return api.batch_ops(ops)
 
     def _run(self, ops: api.BatchOps, async_: bool) -> None:
-        if self.compress == "mxfp8-rows":
+        if self.compress and self.compress.endswith("-rows"):
             self.alloc.quant_strided_batch(ops, async_=async_)
         elif self.compress:
             self.alloc.quant_batch(ops, async_=async_)

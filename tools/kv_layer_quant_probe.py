@@ -10,6 +10,7 @@ of the same swap:
 
 and, for the open question of rows that fill one of a tile's two rounds, the same bytes
 as converting ops of 2048 elements (whole tiles) on dense offsets: full_tiles.
+--format mxfp4 runs the converting forms with MXFP4 records (compress="mxfp4-rows").
 
     python tools/kv_layer_quant_probe.py --hbm --out out/kv_layer_quant_probe.json
 
@@ -74,12 +75,12 @@ def stats(samples):
             "host_us": round(host[len(host) // 2], 1), "host_us_min_max": [round(host[0], 1), round(host[-1], 1)]}
 
 
-def case(label, n_daemons, n_swap, warmup, reps):
+def case(label, n_daemons, n_swap, warmup, reps, fmt="mxfp8"):
     rng = random.Random(0)
     rows = []
     with Mesh(n_daemons, gpus=[0] * n_daemons, policy="stripe") as m:
         with api.Client(daemon_rank=0, gpu=0, ns=m.ns) as c:
-            kv = PagedKVOffload(c, n_swap, n_swap, BLOCK, layers=LAYERS, compress="mxfp8-rows")
+            kv = PagedKVOffload(c, n_swap, n_swap, BLOCK, layers=LAYERS, compress=fmt + "-rows")
             plain = PagedKVOffload(c, n_swap, n_swap, BLOCK, layers=LAYERS)
             kv.gpu_cache.normal_()
             plain.gpu_cache.normal_()
@@ -90,17 +91,17 @@ def case(label, n_daemons, n_swap, warmup, reps):
             # both converting forms compute the same bytes: out strided and back expanded gives what
             # out expanded and back strided gives
             kv.alloc.quant_strided_batch(kv._ops(pairs, put=True))
-            kv.alloc.quant_batch(api.quant_ops(expand(kv, back, False), kv.dtype))
+            kv.alloc.quant_batch(api.quant_ops(expand(kv, back, False), kv.dtype, fmt))
             once = kv.gpu_cache.clone()
-            kv.alloc.quant_batch(api.quant_ops(expand(kv, pairs, True), kv.dtype))
+            kv.alloc.quant_batch(api.quant_ops(expand(kv, pairs, True), kv.dtype, fmt))
             kv.alloc.quant_strided_batch(kv._ops(back, put=False))
             assert torch.equal(kv.gpu_cache.view(torch.int16), once.view(torch.int16)), "the two converting forms differ"
             del once
             for direction, put, pr in (("swap_out", True, pairs), ("swap_in", False, back)):
                 lists = {"quant_strided": kv._ops(pr, put=put),
-                         "expanded_quant": api.quant_ops(expand(kv, pr, put), kv.dtype),
+                         "expanded_quant": api.quant_ops(expand(kv, pr, put), kv.dtype, fmt),
                          "strided_copy": plain._ops(pr, put=put),
-                         "full_tiles": api.quant_ops(full_tiles(kv, n_swap, put), kv.dtype)}
+                         "full_tiles": api.quant_ops(full_tiles(kv, n_swap, put), kv.dtype, fmt)}
                 ways = {"quant_strided": (kv.alloc, lambda: kv.alloc.quant_strided_batch(lists["quant_strided"], async_=True)),
                         "expanded_quant": (kv.alloc, lambda: kv.alloc.quant_batch(lists["expanded_quant"], async_=True)),
                         "strided_copy": (plain.alloc, lambda: plain.alloc.strided_batch(lists["strided_copy"], async_=True)),
@@ -113,7 +114,7 @@ def case(label, n_daemons, n_swap, warmup, reps):
                             samples[k].append(s)
                 row = {"case": label, "direction": direction, "blocks": n_swap, "layers": LAYERS, "row_elems": kv.block_elems,
                        "pool_tiers": tiers, "source_bytes": n_swap * LAYERS * kv.block_bytes,
-                       "record_bytes": n_swap * LAYERS * api.quant_bytes(kv.block_elems), "warmup": warmup, "reps": reps}
+                       "record_bytes": n_swap * LAYERS * api.quant_bytes(kv.block_elems, fmt), "warmup": warmup, "reps": reps}
                 for k in ways:
                     row[k] = {"descriptors": lists[k].n, **stats(samples[k])}
                 lo, hi = row["expanded_quant"]["total_us_min_max"]
@@ -124,6 +125,8 @@ def case(label, n_daemons, n_swap, warmup, reps):
                 row["condition_holds"] = bool(a - b <= hi - lo)
                 row["quant_strided_over_strided_copy"] = round(a / cc, 3)
                 row["bytes_ratio"] = round(33 / 64, 3)
+                if fmt != "mxfp8":
+                    row["format"], row["bytes_ratio"] = fmt, round(17 / 64, 3)
                 row["half_tiles_over_full_tiles"] = round(b / row["full_tiles"]["total_us"], 3)
                 print(json.dumps(row), flush=True)
                 rows.append(row)
@@ -134,6 +137,7 @@ def case(label, n_daemons, n_swap, warmup, reps):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--format", choices=["mxfp8", "mxfp4"], default="mxfp8", help="the record format of the converting forms")
     ap.add_argument("--blocks", type=int, nargs="+", default=[1024, 4096])
     ap.add_argument("--hbm", action="store_true", help="also the same-GPU HBM stand-in (4 daemons on GPU 0)")
     ap.add_argument("--warmup", type=int, default=2)
@@ -145,7 +149,7 @@ def main():
     if args.hbm:
         cases += [("same_gpu_hbm_stand_in_striped3", 4, n) for n in args.blocks]
     for label, n_daemons, n in cases:
-        rows += case(label, n_daemons, n, args.warmup, args.reps)
+        rows += case(label, n_daemons, n, args.warmup, args.reps, args.format)
         if args.out:  # after every case: a later one that fails keeps the earlier results
             os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
             with open(args.out, "w") as f:
