@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 
 #include "ocm/xfer.h"
 
@@ -39,10 +40,28 @@ struct AdamTensor {
                                      // exp_avg_sq in the state space (16-byte aligned)
 };
 constexpr int kAdamMaxTensors = 32;
+
+// The gradient source of ocm_x_adam_multi_acc, appended to the launch arguments: fp32
+// accumulators in the remote half of a pair of their own (usually not the one that holds
+// the moments), a second state space with its own extent table and stripe shift. Element i
+// of tensor k is the word at g_off[k] + 4 i; the gradient is gscale * that word, one fp32
+// multiply rounded on its own. AdamTensor::g is not read.
+#define OCM_ADAM_ACC_ZERO 1u         // store +0.0f over every accumulator word that was read
+struct AdamAccArgs {
+    char *ext[kXferMaxExtents];      // extent bases of the accumulator space
+    uint32_t n_ext;
+    uint32_t unit_shift;             // log2(stripe unit) when n_ext > 1
+    float gscale;
+    uint32_t flags;                  // OCM_ADAM_ACC_*
+    uint32_t host_acc;               // 1: the accumulators are all in the pinned host tier
+    uint32_t host_span;              // (set by the launcher) bytes of the host extent the kernel may touch
+    uint64_t g_off[kAdamMaxTensors]; // byte offset of element 0's accumulator (16-byte aligned), per tensor
+};
 struct AdamMultiArgs {
     AdamArgs c;
     uint32_t count;
     AdamTensor t[kAdamMaxTensors];
+    AdamAccArgs acc;                 // read by the accumulator instantiations only
 };
 static_assert(sizeof(AdamMultiArgs) < 4096, "kernarg segment limit");
 
@@ -96,11 +115,71 @@ inline AdamShape adam_launch_shape(const AdamTensor *t, uint32_t count, bool bf1
     return s;
 }
 
+// The same with the gradient read from accumulators (g_off: one offset per tensor; null:
+// no accumulator space is involved and the answer is adam_launch_shape's). The PCIe
+// variant addresses each space through a buffer resource of its own, so it runs only when
+// both spaces are one pinned host-tier extent whose reach fits 32 bits; any mixed
+// placement takes the generic variant, on the HBM grid rule.
+struct AdamAccShape {
+    AdamShape s;
+    uint64_t acc_span;               // bytes from the accumulator extent's base that the vector part reaches
+};
+
+inline AdamAccShape adam_acc_launch_shape(const AdamTensor *t, const uint64_t *g_off, uint32_t count, bool bf16,
+                                          bool host_state, uint32_t n_ext, bool host_acc, uint32_t acc_n_ext, int cus,
+                                          const AdamKnobs &k) {
+    if (!g_off) return AdamAccShape{adam_launch_shape(t, count, bf16, host_state, n_ext, cus, k), 0};
+    uint64_t span = 0;
+    for (uint32_t i = 0; i < count; i++) span = std::max<uint64_t>(span, g_off[i] + (t[i].n & ~3ull) * 4);
+    const bool acc_fits = host_acc && acc_n_ext == 1 && span < (1ull << 32);
+    return AdamAccShape{adam_launch_shape(t, count, bf16, host_state && acc_fits, n_ext, cus, k), span};
+}
+
+// ---- the accumulator side of one tensor, checked before any launch ----
+// Shared by the host path (csrc/src/lib/optim.cpp) and the stand-alone test program
+// (csrc/tools/ocm_adam_acc_tests.cpp). acc_bytes: the gradient allocation's remote half.
+// same_alloc: it is the allocation that holds the state, so the accumulators must keep clear
+// of this tensor's exp_avg, exp_avg_sq and (bf16) master weights. Every range is tested as
+// bytes <= size - offset with n bounded first, so nothing here can overflow.
+enum AdamAccBad { ADAM_ACC_OK = 0, ADAM_ACC_ALIGN, ADAM_ACC_RANGE, ADAM_ACC_SCALE, ADAM_ACC_FLAGS, ADAM_ACC_OVERLAP };
+
+inline AdamAccBad adam_acc_check(const AdamTensor &t, uint64_t g_off, uint64_t acc_bytes, float gscale, uint32_t flags,
+                                 bool bf16, bool same_alloc) {
+    uint32_t bits;
+    std::memcpy(&bits, &gscale, 4);
+    if ((bits & 0x7f800000u) == 0x7f800000u) return ADAM_ACC_SCALE;
+    if (flags & ~OCM_ADAM_ACC_ZERO) return ADAM_ACC_FLAGS;
+    if (g_off % 16 != 0) return ADAM_ACC_ALIGN;
+    if (t.n > (UINT64_MAX >> 3) || g_off > acc_bytes || 4 * t.n > acc_bytes - g_off) return ADAM_ACC_RANGE;
+    if (same_alloc && t.n) {
+        // two arrays of the same length overlap when their starts are closer than that length
+        const uint64_t bytes = 4 * t.n;
+        auto hits = [&](uint64_t off) { return (off > g_off ? off - g_off : g_off - off) < bytes; };
+        if (hits(t.m_off) || hits(t.v_off) || (bf16 && hits(t.w_off))) return ADAM_ACC_OVERLAP;
+    }
+    return ADAM_ACC_OK;
+}
+
+inline const char *adam_acc_why(AdamAccBad b) {
+    switch (b) {
+    case ADAM_ACC_ALIGN: return "accumulator offset is not a multiple of 16";
+    case ADAM_ACC_RANGE: return "accumulator range exceeds the gradient allocation's remote half";
+    case ADAM_ACC_SCALE: return "gscale is not finite";
+    case ADAM_ACC_FLAGS: return "unknown flag bit";
+    case ADAM_ACC_OVERLAP: return "accumulator range overlaps the tensor's state";
+    case ADAM_ACC_OK: break;
+    }
+    return "ok";
+}
+
 // torch.optim.Adam's update (L2 weight decay, bias correction), or AdamW's
 // (decoupled weight decay) with `decoupled`, one pass over every tensor:
 // reads p, g (local) and m, v (remote), writes p (local) and m, v (remote).
 // bf16 mode: the update runs on the fp32 master weights (remote) and p gets
 // their bf16 rounding (round to nearest even).
-hipError_t adam_remote_launch(const AdamMultiArgs &a, const AdamKnobs &knobs, hipStream_t stream);
+// from_acc: the gradient is gscale * the fp32 accumulators of a.acc (remote), which the same
+// pass zeroes when a.acc.flags has OCM_ADAM_ACC_ZERO; t[].g is not read.
+hipError_t adam_remote_launch(const AdamMultiArgs &a, const AdamKnobs &knobs, hipStream_t stream,
+                              bool from_acc = false);
 
 }  // namespace ocm

@@ -9,6 +9,10 @@
 // once per vector. Lanes keep kV (4) vectors in flight before the first use,
 // which covers the xGMI round trip. The tail (n % 4) is done by lane 0 of
 // the tensor's last workgroup, element by element.
+//
+// kAcc: the gradient is not a local tensor but gscale * fp32 accumulators in a second
+// remote space (AdamAccArgs), loaded in the same first loop with the same kV vectors in
+// flight and, with OCM_ADAM_ACC_ZERO, overwritten with +0 beside the moment stores.
 #include <hip/hip_runtime.h>
 
 #include "ocm/optim.h"
@@ -21,7 +25,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = kAdamThreads;
 
-__device__ __forceinline__ char *state_ptr(const AdamArgs &a, uint64_t x) {
+// Where byte x of a state space lies: AdamArgs (moments, master weights) or AdamAccArgs
+// (gradient accumulators), each with its own extent table and stripe shift.
+template <class Space>
+__device__ __forceinline__ char *state_ptr(const Space &a, uint64_t x) {
     if (a.n_ext == 1) return a.ext[0] + x;
     const uint64_t u = x >> a.unit_shift;
     const uint64_t mask = (1ull << a.unit_shift) - 1;
@@ -46,6 +53,14 @@ __device__ __forceinline__ float adam1(float &p, float g, float &m, float &v, co
     const float denom = sqrtf(v) * a.inv_sqrt_bc2 + a.eps;
     p = p - a.step_size * (m / denom);
     return p;
+}
+
+// The accumulator gradient: one IEEE fp32 multiply, rounded on its own. Contraction is off
+// here whatever -ffp-contract says, so the product never fuses with adam1's g - m or
+// g + wd * p (an fma would round once; gscale == 1 must give acc's bits).
+__device__ __forceinline__ float acc_grad(float gscale, float acc) {
+#pragma clang fp contract(off)
+    return gscale * acc;
 }
 
 // ---- state in the pinned host tier, one extent (kHost) ----
@@ -75,51 +90,63 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
 
 // One launch for up to kAdamMaxTensors parameters (see AdamMultiArgs).
 // kHost: the state is one pinned host-tier extent whose offsets fit 32 bits:
-// buffer loads, write-through (sc1) stores into host memory (above).
-template <bool kBf16, bool kHost, int kV = 4>
+// buffer loads, write-through (sc1) stores into host memory (above). With kAcc the
+// accumulators are such an extent too, behind a buffer resource of their own.
+template <bool kBf16, bool kHost, int kV = 4, bool kAcc = false>
 __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
     const AdamTensor &T = a.t[blockIdx.y];  // uniform: scalar loads from the kernarg segment
     const AdamArgs &c = a.c;
+    const AdamAccArgs &ga = a.acc;
+    const uint64_t g_off = kAcc ? ga.g_off[blockIdx.y] : 0;
+    const bool zero = kAcc && (ga.flags & OCM_ADAM_ACC_ZERO);
     const uint64_t nvec = T.n >> 2;
     const uint64_t lanes = (uint64_t)gridDim.x * kThreads;
     const uint64_t tid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    __amdgpu_buffer_rsrc_t rs;
+    __amdgpu_buffer_rsrc_t rs, grs;
     if constexpr (kHost) rs = __builtin_amdgcn_make_buffer_rsrc(c.ext[0], 0, (int)c.host_span, 0x00020000);
-    auto host_ld = [&](uint64_t off) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(uint32_t)off, 0, kAuxNT));
+    if constexpr (kHost && kAcc) grs = __builtin_amdgcn_make_buffer_rsrc(ga.ext[0], 0, (int)ga.host_span, 0x00020000);
+    auto host_ld = [](__amdgpu_buffer_rsrc_t r, uint64_t off) {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(uint32_t)off, 0, kAuxNT));
     };
-    auto host_st = [&](uint64_t off, f32x4 x) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs, (int)(uint32_t)off, 0, kAuxSC1);
+    auto host_st = [](__amdgpu_buffer_rsrc_t r, uint64_t off, f32x4 x) {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), r, (int)(uint32_t)off, 0, kAuxSC1);
     };
     for (uint64_t base = tid; base < nvec; base += lanes * kV) {
         f32x4 w[kV], m[kV], v[kV], g[kV];
-        f32x4 *wp[kV], *mp[kV], *vp[kV];
+        f32x4 *wp[kV], *mp[kV], *vp[kV], *gp[kV];
 #pragma unroll
         for (int k = 0; k < kV; k++) {
             const uint64_t i = base + (uint64_t)k * lanes;
             if (i < nvec) {
                 if constexpr (kHost) {
-                    m[k] = host_ld(T.m_off + (i << 4));
-                    v[k] = host_ld(T.v_off + (i << 4));
+                    m[k] = host_ld(rs, T.m_off + (i << 4));
+                    v[k] = host_ld(rs, T.v_off + (i << 4));
+                    if constexpr (kAcc) g[k] = host_ld(grs, g_off + (i << 4));
                 } else {
                     mp[k] = reinterpret_cast<f32x4 *>(state_ptr(c, T.m_off + (i << 4)));
                     vp[k] = reinterpret_cast<f32x4 *>(state_ptr(c, T.v_off + (i << 4)));
                     m[k] = __builtin_nontemporal_load(mp[k]);
                     v[k] = __builtin_nontemporal_load(vp[k]);
+                    if constexpr (kAcc) {
+                        gp[k] = reinterpret_cast<f32x4 *>(state_ptr(ga, g_off + (i << 4)));
+                        g[k] = __builtin_nontemporal_load(gp[k]);
+                    }
                 }
                 if constexpr (kBf16) {
                     if constexpr (kHost) {
-                        w[k] = host_ld(T.w_off + (i << 4));
+                        w[k] = host_ld(rs, T.w_off + (i << 4));
                     } else {
                         wp[k] = reinterpret_cast<f32x4 *>(state_ptr(c, T.w_off + (i << 4)));
                         w[k] = __builtin_nontemporal_load(wp[k]);
                     }
-                    const u16x4 gh = __builtin_nontemporal_load(reinterpret_cast<const u16x4 *>(T.g) + i);
+                    if constexpr (!kAcc) {
+                        const u16x4 gh = __builtin_nontemporal_load(reinterpret_cast<const u16x4 *>(T.g) + i);
 #pragma unroll
-                    for (int j = 0; j < 4; j++) g[k][j] = bf16_to_f32(gh[j]);
+                        for (int j = 0; j < 4; j++) g[k][j] = bf16_to_f32(gh[j]);
+                    }
                 } else {
                     w[k] = reinterpret_cast<const f32x4 *>(T.p)[i];
-                    g[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(T.g) + i);
+                    if constexpr (!kAcc) g[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(T.g) + i);
                 }
             }
         }
@@ -130,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     float wj = w[k][j], mj = m[k][j], vj = v[k][j];
-                    adam1(wj, g[k][j], mj, vj, c);
+                    adam1(wj, kAcc ? acc_grad(ga.gscale, g[k][j]) : g[k][j], mj, vj, c);
                     w[k][j] = wj;
                     m[k][j] = mj;
                     v[k][j] = vj;
@@ -141,18 +168,22 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
                     for (int j = 0; j < 4; j++) out[j] = f32_to_bf16(w[k][j]);
                     reinterpret_cast<u16x4 *>(T.p)[i] = out;
                     if constexpr (kHost)
-                        host_st(T.w_off + (i << 4), w[k]);
+                        host_st(rs, T.w_off + (i << 4), w[k]);
                     else
                         __builtin_nontemporal_store(w[k], wp[k]);
                 } else {
                     reinterpret_cast<f32x4 *>(T.p)[i] = w[k];
                 }
                 if constexpr (kHost) {
-                    host_st(T.m_off + (i << 4), m[k]);
-                    host_st(T.v_off + (i << 4), v[k]);
+                    host_st(rs, T.m_off + (i << 4), m[k]);
+                    host_st(rs, T.v_off + (i << 4), v[k]);
+                    if constexpr (kAcc)
+                        if (zero) host_st(grs, g_off + (i << 4), f32x4{0.f, 0.f, 0.f, 0.f});
                 } else {
                     __builtin_nontemporal_store(m[k], mp[k]);
                     __builtin_nontemporal_store(v[k], vp[k]);
+                    if constexpr (kAcc)
+                        if (zero) __builtin_nontemporal_store(f32x4{0.f, 0.f, 0.f, 0.f}, gp[k]);
                 }
             }
         }
@@ -162,11 +193,17 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
             float *mq = reinterpret_cast<float *>(state_ptr(c, T.m_off + 4 * i));
             float *vq = reinterpret_cast<float *>(state_ptr(c, T.v_off + 4 * i));
             float mj = *mq, vj = *vq, wj, gj;
-            if constexpr (kBf16) {
+            if constexpr (kBf16)
                 wj = *reinterpret_cast<float *>(state_ptr(c, T.w_off + 4 * i));
+            else
+                wj = static_cast<float *>(T.p)[i];
+            if constexpr (kAcc) {
+                float *gq = reinterpret_cast<float *>(state_ptr(ga, g_off + 4 * i));
+                gj = acc_grad(ga.gscale, *gq);
+                if (zero) *gq = 0.f;
+            } else if constexpr (kBf16) {
                 gj = bf16_to_f32(static_cast<const unsigned short *>(T.g)[i]);
             } else {
-                wj = static_cast<float *>(T.p)[i];
                 gj = static_cast<const float *>(T.g)[i];
             }
             adam1(wj, gj, mj, vj, c);
@@ -182,36 +219,47 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
     }
 }
 
+// The instantiation for a shape: every variant has a twin that reads accumulators.
+template <bool kAcc>
+auto adam_kernel_for(bool bf16, const AdamShape &s) -> void (*)(AdamMultiArgs) {
+    if (bf16) return s.host ? adam_multi_kernel<true, true, 4, kAcc> : adam_multi_kernel<true, false, 4, kAcc>;
+    if (!s.host) return adam_multi_kernel<false, false, 4, kAcc>;
+    return s.kV == 2   ? adam_multi_kernel<false, true, 2, kAcc>
+           : s.kV == 8 ? adam_multi_kernel<false, true, 8, kAcc>
+                       : adam_multi_kernel<false, true, 4, kAcc>;
+}
+
 }  // namespace
 
-hipError_t adam_remote_launch(const AdamMultiArgs &a, const AdamKnobs &knobs, hipStream_t stream) {
+hipError_t adam_remote_launch(const AdamMultiArgs &a, const AdamKnobs &knobs, hipStream_t stream, bool from_acc) {
     if (a.count == 0) return hipSuccess;
     if (a.count > (uint32_t)kAdamMaxTensors) return hipErrorInvalidValue;
     if (a.c.n_ext < 1 || a.c.n_ext > (uint32_t)kXferMaxExtents) return hipErrorInvalidValue;
     if (a.c.n_ext > 1 && a.c.unit_shift < 4) return hipErrorInvalidValue;
+    if (from_acc && (a.acc.n_ext < 1 || a.acc.n_ext > (uint32_t)kXferMaxExtents ||
+                     (a.acc.n_ext > 1 && a.acc.unit_shift < 4)))
+        return hipErrorInvalidValue;
     for (uint32_t k = 0; k < a.count; k++) {
         const AdamTensor &t = a.t[k];
         const uintptr_t pal = a.c.bf16 ? 7u : 15u;
-        if ((((uintptr_t)t.p | (uintptr_t)t.g) & pal) || ((t.m_off | t.v_off | (a.c.bf16 ? t.w_off : 0)) & 15u))
+        const uintptr_t g = from_acc ? (uintptr_t)a.acc.g_off[k] & 15u : (uintptr_t)t.g & pal;
+        if (((uintptr_t)t.p & pal) || g || ((t.m_off | t.v_off | (a.c.bf16 ? t.w_off : 0)) & 15u))
             return hipErrorInvalidValue;
     }
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
         cus = 256;
-    const AdamShape s = adam_launch_shape(a.t, a.count, a.c.bf16, a.c.host_state, a.c.n_ext, cus, knobs);
+    const AdamAccShape as = adam_acc_launch_shape(a.t, from_acc ? a.acc.g_off : nullptr, a.count, a.c.bf16,
+                                                  a.c.host_state, a.c.n_ext, a.acc.host_acc, a.acc.n_ext, cus, knobs);
+    const AdamShape &s = as.s;
     if (s.gx == 0) return hipSuccess;
-    void (*kernel)(AdamMultiArgs) = adam_multi_kernel<false, false>;
-    if (a.c.bf16)
-        kernel = s.host ? adam_multi_kernel<true, true> : adam_multi_kernel<true, false>;
-    else if (s.host)
-        kernel = s.kV == 2   ? adam_multi_kernel<false, true, 2>
-                 : s.kV == 8 ? adam_multi_kernel<false, true, 8>
-                             : adam_multi_kernel<false, true>;
+    void (*kernel)(AdamMultiArgs) = from_acc ? adam_kernel_for<true>(a.c.bf16, s) : adam_kernel_for<false>(a.c.bf16, s);
     const dim3 grid(s.gx, a.count);
     if (s.host) {
         AdamMultiArgs h = a;
         h.c.host_span = (uint32_t)s.span;  // below 2^32, or the host variant would not run
+        h.acc.host_span = (uint32_t)as.acc_span;  // likewise (0 without accumulators)
         hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, h);
     } else {
         hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, a);

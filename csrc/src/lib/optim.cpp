@@ -7,6 +7,8 @@
 // complements are the caller's, computed in double from the exact betas like the bias
 // corrections: 1.f - float(0.999) is 1.3e-5 short of float(0.001).
 // Queued on `stream` (e.g. torch's current stream); no host wait.
+// ocm_x_adam_multi_acc takes the gradient from fp32 accumulators in the remote half of a
+// second pair instead (ocm/optim.h: AdamAccArgs), scaled, and can zero them in the same pass.
 #include <cmath>
 
 #include "internal.h"
@@ -22,12 +24,21 @@ namespace {
 // the hyper-parameters, where the state lives). adam_run words the errors.
 enum AdamBad { ADAM_OK = 0, ADAM_NO_GPU, ADAM_NO_PAIR, ADAM_EXTENTS, ADAM_STRIPE };
 
-AdamBad adam_prepare(ocm_alloc_t a, const float hp[9], bool bf16, AdamArgs *x) {
+// One state space (the moments' pair or the accumulators'): Space is AdamArgs or AdamAccArgs.
+template <class Space>
+AdamBad adam_space(ocm_alloc_t a, Space *x) {
     if (S().device < 0) return ADAM_NO_GPU;
     if (!is_pair(a->kind) || a->ext.empty() || !a->all_dev_ok) return ADAM_NO_PAIR;
     if (a->ext.size() > (size_t)kXferMaxExtents) return ADAM_EXTENTS;
     std::memset(x, 0, sizeof(*x));
     if (pair_side(a, 4, x) < 0) return ADAM_STRIPE;
+    return ADAM_OK;
+}
+
+bool host_tier(ocm_alloc_t a) { return !a->any_gpu && !a->any_net; }
+
+AdamBad adam_prepare(ocm_alloc_t a, const float hp[9], bool bf16, AdamArgs *x) {
+    if (const AdamBad bad = adam_space(a, x)) return bad;
     x->b1 = hp[0];
     x->b2 = hp[1];
     x->eps = hp[2];
@@ -38,7 +49,7 @@ AdamBad adam_prepare(ocm_alloc_t a, const float hp[9], bool bf16, AdamArgs *x) {
     x->decay = hp[6];
     x->omb1 = hp[7];
     x->omb2 = hp[8];
-    x->host_state = (!a->any_gpu && !a->any_net) ? 1u : 0u;
+    x->host_state = host_tier(a) ? 1u : 0u;
     x->bf16 = bf16 ? 1u : 0u;
     return ADAM_OK;
 }
@@ -48,21 +59,37 @@ bool fits(ocm_alloc_t a, uint64_t off, uint64_t n) {
     return n <= (UINT64_MAX >> 3) && off <= a->remote_bytes && 4 * n <= a->remote_bytes - off;
 }
 
-// The one path behind the three entry points: `count` tensors, kAdamMaxTensors per launch.
-// `who` names the caller in the messages; the list entry point (`multi`) words some of them
-// its own way and names the tensor at fault. Every tensor is checked before the first
-// launch: a bad one never leaves some parameters a step ahead of the others.
+// Where the gradient comes from when it is not a local tensor (ocm_x_adam_multi_acc).
+struct AdamAccSource {
+    ocm_alloc_t grads;
+    const uint64_t *g_off;
+    float gscale;
+    uint32_t flags;
+};
+
+// The one path behind the four entry points: `count` tensors, kAdamMaxTensors per launch.
+// `who` names the caller in the messages; the list entry points (`multi`) word some of them
+// their own way and name the tensor at fault. `acc`: the gradients are accumulators (`g` is
+// then unused). Every tensor is checked before the first launch: a bad one never leaves
+// some parameters a step ahead of the others.
 int adam_run(const char *who, bool multi, ocm_alloc_t a, int count, void *const *p, const void *const *g,
              const uint64_t *n, const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[9],
-             bool bf16, void *stream) {
+             bool bf16, void *stream, const AdamAccSource *acc = nullptr) {
     State &s = S();
-    if (!a || count < 0 || (count && (!p || !g || !n || !m_off || !v_off || (bf16 && !w_off))) || !hp ||
-        (!multi && (!p[0] || !g[0])))
+    if (!a || count < 0 || (count && (!p || (!acc && !g) || !n || !m_off || !v_off || (bf16 && !w_off))) || !hp ||
+        (!multi && (!p[0] || !g[0])) || (acc && (!acc->grads || (count && !acc->g_off))))
         OCM_FAIL(-1, "%s: null argument", who);
     AdamMultiArgs x;
     std::memset(&x, 0, sizeof(x));
     const char *const which = multi ? "" : " (HBM or host tier, not another node)";
-    switch (adam_prepare(a, hp, bf16, &x.c)) {
+    AdamBad bad = adam_prepare(a, hp, bf16, &x.c);
+    if (bad == ADAM_OK && acc) {  // the same checks, the same wording, for the gradient allocation
+        bad = adam_space(acc->grads, &x.acc);
+        x.acc.gscale = acc->gscale;
+        x.acc.flags = acc->flags;
+        x.acc.host_acc = host_tier(acc->grads) ? 1u : 0u;
+    }
+    switch (bad) {
     case ADAM_NO_GPU: OCM_FAIL(-1, "%s needs a GPU", who);
     case ADAM_EXTENTS:
         if (!multi) OCM_FAIL(-1, "%s: too many extents", who);
@@ -74,23 +101,31 @@ int adam_run(const char *who, bool multi, ocm_alloc_t a, int count, void *const 
     case ADAM_OK: break;
     }
     for (int i = 0; i < count; i++) {
-        if (!p[i] || !g[i]) OCM_FAIL(-1, "%s: tensor %d has no data", who, i);
-        if (fits(a, m_off[i], n[i]) && fits(a, v_off[i], n[i]) && (!bf16 || fits(a, w_off[i], n[i]))) continue;
-        if (multi) OCM_FAIL(-1, "%s: tensor %d state range exceeds the remote half", who, i);
-        OCM_FAIL(-1, "%s: state range exceeds the remote half (%zu bytes)", who, a->remote_bytes);
+        if (!p[i] || (!acc && !g[i])) OCM_FAIL(-1, "%s: tensor %d has no data", who, i);
+        if (!(fits(a, m_off[i], n[i]) && fits(a, v_off[i], n[i]) && (!bf16 || fits(a, w_off[i], n[i])))) {
+            if (multi) OCM_FAIL(-1, "%s: tensor %d state range exceeds the remote half", who, i);
+            OCM_FAIL(-1, "%s: state range exceeds the remote half (%zu bytes)", who, a->remote_bytes);
+        }
+        if (!acc) continue;
+        const AdamTensor t{p[i], nullptr, n[i], bf16 ? w_off[i] : 0, m_off[i], v_off[i]};
+        const AdamAccBad why = adam_acc_check(t, acc->g_off[i], acc->grads->remote_bytes, acc->gscale, acc->flags, bf16,
+                                              acc->grads == a);
+        if (why != ADAM_ACC_OK) OCM_FAIL(-1, "%s: tensor %d: %s", who, i, adam_acc_why(why));
     }
     std::lock_guard<std::recursive_mutex> lk(s.mu);
     const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
     if (wait_alloc(a) != 0) return -1;  // queued async ops on this allocation come first
+    if (acc && acc->grads != a && wait_alloc(acc->grads) != 0) return -1;  // the accumulates, for one
     DeviceGuard dg(s.device);
     before_launch();
     for (int k0 = 0; k0 < count; k0 += kAdamMaxTensors) {
         x.count = (uint32_t)std::min(count - k0, kAdamMaxTensors);
         for (uint32_t j = 0; j < x.count; j++) {
             const int i = k0 + (int)j;
-            x.t[j] = AdamTensor{p[i], g[i], n[i], bf16 ? w_off[i] : 0, m_off[i], v_off[i]};
+            x.t[j] = AdamTensor{p[i], acc ? nullptr : g[i], n[i], bf16 ? w_off[i] : 0, m_off[i], v_off[i]};
+            if (acc) x.acc.g_off[j] = acc->g_off[i];
         }
-        const hipError_t e = adam_remote_launch(x, knobs, static_cast<hipStream_t>(stream));
+        const hipError_t e = adam_remote_launch(x, knobs, static_cast<hipStream_t>(stream), acc != nullptr);
         if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
     }
     return 0;
@@ -122,6 +157,18 @@ int ocm_x_adam_multi(ocm_alloc_t a, int count, void *const *p, const void *const
                      const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[9],
                      int bf16, void *stream) {
     return adam_run("ocm_x_adam_multi", true, a, count, p, g, n, w_off, m_off, v_off, hp, bf16 != 0, stream);
+}
+
+// The same with every gradient read from the fp32 accumulators of `grads`' remote half
+// (tensor i's at byte offset g_off[i]) as gscale * acc, one fp32 multiply rounded on its own;
+// flags & OCM_ADAM_ACC_ZERO stores +0 over the accumulators in the same pass. `grads` may be
+// `state` itself when the ranges keep clear of each other.
+int ocm_x_adam_multi_acc(ocm_alloc_t state, ocm_alloc_t grads, int count, void *const *p, const uint64_t *n,
+                         const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const uint64_t *g_off,
+                         const float hp[9], float gscale, uint32_t flags, int bf16, void *stream) {
+    const AdamAccSource acc{grads, g_off, gscale, flags};
+    return adam_run("ocm_x_adam_multi_acc", true, state, count, p, nullptr, n, w_off, m_off, v_off, hp, bf16 != 0,
+                    stream, &acc);
 }
 
 }  // extern "C"

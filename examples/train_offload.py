@@ -8,9 +8,11 @@ runs on the CPU with the state in the daemons' host tier.
 
 With --accum N every step sums N micro-batches' gradients in disaggregated memory too
 (models.OffloadedGradAccumulator: fp32 accumulators in the remote half, one one-sided
-accumulate per micro-batch) and hands the optimizer their mean.
+accumulate per micro-batch) and hands the optimizer their mean. With --accum-in-place (GPU)
+the fused Adam kernel reads that mean from the accumulators itself and zeroes them in the same
+pass: no read-back region, no copy into .grad and no zeroing pass after the first.
 
-    python examples/train_offload.py [--gpu 0] [--bf16] [--steps 200] [--accum 4]
+    python examples/train_offload.py [--gpu 0] [--bf16] [--steps 200] [--accum 4 [--accum-in-place]]
 """
 import argparse
 import os
@@ -32,7 +34,11 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--daemons", type=int, default=3)
     ap.add_argument("--accum", type=int, default=0, help="micro-batches per step, summed in disaggregated memory")
+    ap.add_argument("--accum-in-place", action="store_true",
+                    help="with --accum: the optimizer reads (and zeroes) the remote accumulators itself")
     args = ap.parse_args()
+    if args.accum_in_place and args.accum <= 0:
+        ap.error("--accum-in-place goes with --accum N")
     on_gpu = args.gpu is not None
     dev = f"cuda:{args.gpu}" if on_gpu else "cpu"
     dtype = torch.bfloat16 if args.bf16 else torch.float32
@@ -46,7 +52,7 @@ def main():
             tiers = sorted({e["tier"] for e in opt.allocs[0].remote_info()["extents"]})
             first = last = None
             params = list(model.parameters())
-            acc = OffloadedGradAccumulator(params, c) if args.accum > 0 else None
+            acc = OffloadedGradAccumulator(params, c, readback=not args.accum_in_place) if args.accum > 0 else None
 
             def micro_batch():
                 x = torch.randn(256, 64, device=dev)
@@ -56,7 +62,8 @@ def main():
 
             for step in range(args.steps):
                 if acc:
-                    acc.zero()
+                    if not args.accum_in_place:
+                        acc.zero()
                     total = 0.0
                     for _ in range(args.accum):
                         loss = micro_batch()
@@ -64,11 +71,14 @@ def main():
                         loss.backward()
                         acc.add(scale=1.0 / args.accum)  # remote fp32 += grad / N, one launch
                         total += loss.item()
-                    sums = acc.read()
-                    with torch.no_grad():
-                        for p, g in zip(params, sums):
-                            p.grad.copy_(g)  # the mean gradient, rounded once into the parameter's dtype
-                    opt.step()
+                    if args.accum_in_place:
+                        opt.step(accumulator=acc)  # g = the fp32 accumulators, zeroed by the same kernel
+                    else:
+                        sums = acc.read()
+                        with torch.no_grad():
+                            for p, g in zip(params, sums):
+                                p.grad.copy_(g)  # the mean gradient, rounded once into the parameter's dtype
+                        opt.step()
                     step_loss = total / args.accum  # the step's loss: the mean over its micro-batches
                 else:
                     loss = micro_batch()

@@ -265,6 +265,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                                        ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                        ctypes.POINTER(ctypes.c_float), i32, vp]),
             "ocm_x_adam_bf16": (i32, [vp, vp, vp, u64, u64, u64, u64, ctypes.POINTER(ctypes.c_float), vp]),
+            "ocm_x_adam_multi_acc": (i32, [vp, vp, i32, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                           ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                           ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_uint32, i32, vp]),
             "ocm_x_set_tuning": (None, [i32, i32, i32]),
             "ocm_x_set_tuning_dir": (i32, [i32, i32, i32, i32]),
             "ocm_x_batch": (i32, [i32, vp, ctypes.POINTER(vp), i32, u64, ctypes.POINTER(u64), i32, i32]),
@@ -312,6 +315,7 @@ COUNTER_KEYS = ["n_put", "n_get", "bytes_put", "bytes_get", "n_alloc", "n_free",
                 "n_quant", "n_quant_ops", "bytes_quant_src", "bytes_quant_wire",
                 "n_strided", "n_strided_ops", "bytes_strided"]
 OCM_BATCH_ASYNC = 1
+OCM_ADAM_ACC_ZERO = 1  # ocm_x_adam_multi_acc: store +0 over the accumulators in the same pass
 OCM_QUANT_BF16 = 1
 OCM_QUANT_FP16 = 2
 OCM_QUANT_MXFP8 = 0  # enum ocm_quant_format: bits 8 to 15 of a converting op's dtype word
@@ -1056,6 +1060,27 @@ class Allocation:
             (ctypes.c_float * 9)(*hp), 1 if bf16 else 0, self._stream_handle(stream))
         if rc != 0:
             raise OcmError("ocm_x_adam_multi: " + last_error())
+
+    def adam_multi_acc(self, ps, grads_alloc, g_offs, m_offs, v_offs, hp, gscale: float = 1.0, zero: bool = True,
+                       w_offs=None, stream=None) -> None:
+        """ocm_x_adam_multi_acc: adam_multi with every gradient read from fp32 accumulators in the
+        remote half of `grads_alloc` (an Allocation, possibly this one), tensor i's at byte offset
+        g_offs[i]: g = fl32(gscale * acc), fp32 also for bfloat16 parameters (the master update
+        sees it unrounded). zero: the same pass stores +0 over the accumulators it read."""
+        import torch
+
+        k = len(ps)
+        bf16 = k > 0 and ps[0].dtype == torch.bfloat16
+        if bf16 and w_offs is None:
+            raise ValueError("bf16 parameters need w_offs (fp32 master weights)")
+        arr_v, arr_u = ctypes.c_void_p * k, ctypes.c_uint64 * k
+        hp = _adam_hp(hp)
+        rc = self._c.lib.ocm_x_adam_multi_acc(
+            self.handle, grads_alloc.handle, k, arr_v(*[t.data_ptr() for t in ps]), arr_u(*[t.numel() for t in ps]),
+            arr_u(*(w_offs or [0] * k)), arr_u(*m_offs), arr_u(*v_offs), arr_u(*g_offs), (ctypes.c_float * 9)(*hp),
+            float(gscale), OCM_ADAM_ACC_ZERO if zero else 0, 1 if bf16 else 0, self._stream_handle(stream))
+        if rc != 0:
+            raise OcmError("ocm_x_adam_multi_acc: " + last_error())
 
     def time_onesided(self, op_flag: int, nbytes: int, iters: int, local_offset: int = 0, remote_offset: int = 0) -> float:
         """Seconds per blocking one-sided op, timed inside the native library."""

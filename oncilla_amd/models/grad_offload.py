@@ -14,6 +14,15 @@ Local half::
 
     [ flat gradients, each tensor padded to 4 elements | fp32 read-back region ]
 
+With ``readback=False`` the read-back region, 4 bytes per parameter of local HBM, gives way to
+one chunk of zeros of at most 4 MiB::
+
+    [ flat gradients, each tensor padded to 4 elements | zero chunk ]
+
+``read()`` then raises: the consumer is ``OffloadedAdam.step(accumulator=...)``, whose kernel
+reads the accumulators where they are and zeroes them in the same pass, so ``zero()`` (one
+batch of puts from the chunk) runs only when the accumulator is built.
+
 Streams: ``add`` waits for work already queued on torch's current stream (the backward
 that wrote the gradients), and after an async ``add`` that stream waits for the
 accumulate before anything overwrites them (``zero_grads``, the next backward).
@@ -34,8 +43,10 @@ def _pad(n: int, to: int) -> int:
 class OffloadedGradAccumulator:
     """Parameters' gradients (local half) + their fp32 accumulators (remote half)."""
 
+    _ZERO_CHUNK = 4 << 20  # readback=False: at most this many bytes of zeros in the local half
+
     def __init__(self, params: Iterable, client: api.Client, kind: int = None, flags: int = api.OCM_ALLOC_STRIPE,
-                 stripe_unit: int = 0, remote_rank: int = -1):
+                 stripe_unit: int = 0, remote_rank: int = -1, readback: bool = True):
         import torch
 
         self.params = [p for p in params if p.requires_grad]
@@ -63,7 +74,9 @@ class OffloadedGradAccumulator:
             lo += n * size
         self.total_elems = e
         self.grad_bytes = _pad(lo, 16)
-        self.local_bytes = self.grad_bytes + 4 * e
+        self.readback = readback
+        self.zero_bytes = min(4 * e, self._ZERO_CHUNK)  # readback=False: the zero chunk
+        self.local_bytes = self.grad_bytes + (4 * e if readback else self.zero_bytes)
         self.alloc = client.alloc(kind, local_bytes=self.local_bytes, remote_bytes=4 * e, remote_rank=remote_rank,
                                   flags=flags, stripe_unit=stripe_unit)
         self._runs = np.asarray(runs, dtype=np.int64)
@@ -104,6 +117,8 @@ class OffloadedGradAccumulator:
     def read(self) -> list:
         """The accumulators, fetched into the read-back region: one fp32 view per parameter,
         valid until the next read() or zero()."""
+        if not self.readback:
+            raise RuntimeError("read() needs the read-back region (readback=True)")
         self.alloc.stream_wait()  # earlier readers of the region on torch's stream
         self.alloc.get(self.grad_bytes, 0, 4 * self.total_elems)
         return [self._readback[e: e + n].view(p.shape) for p, e, _, n in self._slots]
@@ -112,7 +127,11 @@ class OffloadedGradAccumulator:
         """Reset every accumulator to +0."""
         self._readback.zero_()
         self.alloc.stream_wait()
-        self.alloc.put(self.grad_bytes, 0, 4 * self.total_elems)
+        if self.readback:
+            self.alloc.put(self.grad_bytes, 0, 4 * self.total_elems)
+            return
+        total, z = 4 * self.total_elems, self.zero_bytes  # one batch of puts (op_flag 1) from the zero chunk
+        self.alloc.batch([(1, self.grad_bytes, off, min(z, total - off)) for off in range(0, total, z)])
 
     def wait(self) -> None:
         self.alloc.wait()

@@ -28,6 +28,13 @@ weights next to the moments in remote memory (mixed precision: 4 bytes per
 parameter stay local, bf16 p and g; 12 go remote). mode="staged" is the path above (CPU
 processes, and state on another node, which a kernel cannot address).
 
+step(accumulator=acc) joins the fused kernel to gradient accumulation in remote memory
+(grad_offload.OffloadedGradAccumulator): the same launches read every gradient from acc's
+fp32 accumulators as fl32(scale * acc), a third remote array streamed beside the moments, and
+store +0 back over them (ocm_x_adam_multi_acc). No fp32 gradient copy in local HBM, no
+read-back, no separate zeroing pass; for bfloat16 parameters the gradient reaches the fp32
+master update unrounded.
+
 The update is torch.optim.Adam's (L2 weight decay, bias correction; reference
 behaviour: torch/optim/adam.py single-tensor path), so results match it to
 float32 rounding (tests/test_optim_offload.py). The reference runtime has no
@@ -138,10 +145,13 @@ class OffloadedAdam:
                     torch.cuda.current_stream(client.device).synchronize()  # the copy, before the put reads buf
                     a.put(0, 4 * (2 * self.padded + start + e0), 4 * (e1 - e0))
 
-    def _step_fused(self) -> None:
+    def _hp(self) -> tuple:
         b1, b2 = self.betas
-        hp = (b1, b2, self.eps, self.weight_decay, self.lr / (1 - b1 ** self.t), 1 / math.sqrt(1 - b2 ** self.t),
-              (1 - self.lr * self.weight_decay) if self.decoupled else math.nan)  # NaN: L2 Adam
+        return (b1, b2, self.eps, self.weight_decay, self.lr / (1 - b1 ** self.t), 1 / math.sqrt(1 - b2 ** self.t),
+                (1 - self.lr * self.weight_decay) if self.decoupled else math.nan)  # NaN: L2 Adam
+
+    def _step_fused(self) -> None:
+        hp = self._hp()
         ps, gs, mo, vo, wo = [], [], [], [], []
         for p, start in zip(self.params, self.starts):
             if p.grad is None:
@@ -153,6 +163,19 @@ class OffloadedAdam:
             wo.append(4 * (2 * self.padded + start))
         # every parameter in ceil(n / 32) launches (descriptors in the kernel arguments)
         self.allocs[0].adam_multi(ps, gs, mo, vo, hp, w_offs=wo if self.bf16 else None)
+
+    def _step_accumulator(self, accumulator, scale: float, zero: bool) -> None:
+        """Every parameter's gradient is scale * its fp32 accumulator slot, read (and zeroed) in
+        place by the update kernel; .grad is not consulted."""
+        slots = accumulator._slots
+        if len(slots) != len(self.params) or any(s[0] is not p for s, p in zip(slots, self.params)):
+            raise ValueError("the accumulator's parameter list is not this optimizer's, in order")
+        ps = [p.data for p in self.params]
+        mo = [4 * s for s in self.starts]
+        vo = [4 * (self.padded + s) for s in self.starts]
+        wo = [4 * (2 * self.padded + s) for s in self.starts] if self.bf16 else None
+        self.allocs[0].adam_multi_acc(ps, accumulator.alloc, [4 * s[1] for s in slots], mo, vo, self._hp(),
+                                      gscale=scale, zero=zero, w_offs=wo)
 
     def chunk_bytes(self, k: int) -> int:
         """Bytes of chunk k's record: its m half in full, then v up to the chunk's length."""
@@ -188,8 +211,22 @@ class OffloadedAdam:
             denom = (v.sqrt() / math.sqrt(bc2)).add_(self.eps)
             pv.addcdiv_(m, denom, value=-step_size)
 
-    def step(self) -> None:
-        """One Adam step over every parameter; queued on torch's current stream (GPU) without a host wait."""
+    def step(self, accumulator=None, scale: float = 1.0, zero: bool = True) -> None:
+        """One Adam step over every parameter; queued on torch's current stream (GPU) without a host wait.
+
+        accumulator: an OffloadedGradAccumulator over this optimizer's parameters, in order (fused
+        mode only). The gradients are then scale * its fp32 accumulators, read from remote memory
+        by the update kernel itself and, with `zero`, reset to +0 in the same pass."""
+        if accumulator is not None:
+            if self.mode != "fused":
+                raise ValueError("step(accumulator=...) needs mode='fused'")
+            self.t += 1
+            try:
+                self._step_accumulator(accumulator, scale, zero)
+            except Exception:
+                self.t -= 1  # nothing ran: every tensor is checked before the first launch
+                raise
+            return
         self.t += 1
         if self.mode == "fused":
             self._step_fused()
