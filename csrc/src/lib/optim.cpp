@@ -9,9 +9,12 @@
 // Queued on `stream` (e.g. torch's current stream); no host wait.
 // ocm_x_adam_multi_acc takes the gradient from fp32 accumulators in the remote half of a
 // second pair instead (ocm/optim.h: AdamAccArgs), scaled, and can zero them in the same pass.
+// ocm_x_acc_sumsq reduces such accumulators to their sum of squares and non-finite count
+// (ocm/acc_norm.h), from which ocm_x_clip_scale makes that scale for a clipped step.
 #include <cmath>
 
 #include "internal.h"
+#include "ocm/acc_norm.h"
 #include "ocm/optim.h"
 
 using namespace ocm;
@@ -131,9 +134,87 @@ int adam_run(const char *who, bool multi, ocm_alloc_t a, int count, void *const 
     return 0;
 }
 
+// The sum of squares and the non-finite count of `count` accumulator tensors of `grads`' remote
+// half (ocm/acc_norm.h), kAdamMaxTensors per launch pair, the totals formed once by the last
+// finishing kernel. Every tensor is checked before the first launch: a refusal writes nothing.
+int acc_norm_run(const char *who, ocm_alloc_t grads, int count, const uint64_t *n, const uint64_t *g_off, double *sumsq,
+                 uint64_t *nonfinite, void *work, uint64_t work_bytes, void *stream) {
+    State &s = S();
+    if (!grads || (count > 0 && (!n || !g_off || !work)) || !sumsq || !nonfinite) OCM_FAIL(-1, "%s: null argument", who);
+    AccNormArgs x;
+    switch (adam_space(grads, &x)) {  // the Adam hooks' checks, the Adam hooks' wording
+    case ADAM_NO_GPU: OCM_FAIL(-1, "%s needs a GPU", who);
+    case ADAM_EXTENTS:
+    case ADAM_NO_PAIR: OCM_FAIL(-1, "%s needs a remote half this GPU can address", who);
+    case ADAM_STRIPE: OCM_FAIL(-1, "%s: stripe unit unusable", who);
+    case ADAM_OK: break;
+    }
+    x.host_acc = host_tier(grads) ? 1u : 0u;
+    int at = -1;
+    if (const AccNormBad why = acc_norm_check_list(count, n, g_off, grads->remote_bytes, &at)) {
+        if (at < 0) OCM_FAIL(-1, "%s: %s", who, acc_norm_why(why));
+        OCM_FAIL(-1, "%s: tensor %d: %s", who, at, acc_norm_why(why));
+    }
+    std::lock_guard<std::recursive_mutex> lk(s.mu);
+    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
+    DeviceGuard dg(s.device);
+    const uint64_t need = acc_norm_work_bytes(count, acc_norm_cus(), knobs);
+    if (work_bytes < need)
+        OCM_FAIL(-1, "%s: workspace of %llu bytes is short of %llu", who, (unsigned long long)work_bytes,
+                 (unsigned long long)need);
+    if (wait_alloc(grads) != 0) return -1;  // queued async ops on this allocation (the accumulates) come first
+    before_launch();
+    x.work = static_cast<AccNormPartial *>(work);
+    int k0 = 0;
+    do {  // count == 0: the finishing kernel alone, for the zero totals
+        x.count = (uint32_t)std::min(count - k0, kAdamMaxTensors);
+        for (uint32_t j = 0; j < x.count; j++) {
+            x.n[j] = n[k0 + (int)j];
+            x.g_off[j] = g_off[k0 + (int)j];
+        }
+        AccNormFinishArgs f{};
+        f.sumsq = sumsq + k0;
+        f.nonfinite = nonfinite + k0;
+        k0 += (int)x.count;
+        f.totals = k0 >= count ? 1u : 0u;
+        f.total_count = (uint32_t)count;
+        f.all_sumsq = sumsq;
+        f.all_nonfinite = nonfinite;
+        const hipError_t e = acc_norm_launch(x, f, work_bytes, knobs, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
+    } while (k0 < count);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// The global gradient norm's raw material, computed where the accumulators live: for tensor i
+// of n[i] fp32 words at byte offset g_off[i] of `grads`' remote half, sumsq[i] (fp64) and
+// nonfinite[i] (words that are inf or NaN), and at index `count` their totals in index order.
+// sumsq / nonfinite: count + 1 elements of device memory; work: ocm_x_acc_sumsq_work_bytes(count)
+// bytes of device memory, the caller's (two streams never share scratch of the library's).
+// Queued on `stream` behind the async ops queued on `grads`; the accumulators are only read.
+int ocm_x_acc_sumsq(ocm_alloc_t grads, int count, const uint64_t *n, const uint64_t *g_off, double *sumsq,
+                    uint64_t *nonfinite, void *work, uint64_t work_bytes, void *stream) {
+    return acc_norm_run("ocm_x_acc_sumsq", grads, count, n, g_off, sumsq, nonfinite, work, work_bytes, stream);
+}
+
+// Bytes of workspace a list of `count` tensors needs on this GPU (0: none, or no GPU).
+uint64_t ocm_x_acc_sumsq_work_bytes(int count) {
+    State &s = S();
+    if (s.device < 0 || count <= 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(s.mu);
+    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
+    DeviceGuard dg(s.device);
+    return acc_norm_work_bytes(count, acc_norm_cus(), knobs);
+}
+
+// ocm/acc_norm.h's clip_scale: the gscale of a step clipped to max_norm, in double.
+double ocm_x_clip_scale(double sumsq_total, double scale, double max_norm) {
+    return clip_scale(sumsq_total, scale, max_norm);
+}
 
 // One tensor: the count = 1 case of ocm_x_adam_multi, under its own name.
 int ocm_x_adam(ocm_alloc_t a, float *p, const float *g, uint64_t n, uint64_t m_off, uint64_t v_off,

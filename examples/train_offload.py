@@ -10,9 +10,12 @@ With --accum N every step sums N micro-batches' gradients in disaggregated memor
 (models.OffloadedGradAccumulator: fp32 accumulators in the remote half, one one-sided
 accumulate per micro-batch) and hands the optimizer their mean. With --accum-in-place (GPU)
 the fused Adam kernel reads that mean from the accumulators itself and zeroes them in the same
-pass: no read-back region, no copy into .grad and no zeroing pass after the first.
+pass: no read-back region, no copy into .grad and no zeroing pass after the first. With
+--clip-norm X on top of that, every step first reduces the accumulators where they are to their
+global 2-norm (one read-only pass, one host synchronise) and clips the gradient to X through the
+kernel's scale; a step whose accumulators hold an inf or NaN is skipped.
 
-    python examples/train_offload.py [--gpu 0] [--bf16] [--steps 200] [--accum 4 [--accum-in-place]]
+    python examples/train_offload.py [--gpu 0] [--bf16] [--steps 200] [--accum 4 [--accum-in-place [--clip-norm 1.0]]]
 """
 import argparse
 import os
@@ -36,9 +39,13 @@ def main():
     ap.add_argument("--accum", type=int, default=0, help="micro-batches per step, summed in disaggregated memory")
     ap.add_argument("--accum-in-place", action="store_true",
                     help="with --accum: the optimizer reads (and zeroes) the remote accumulators itself")
+    ap.add_argument("--clip-norm", type=float, default=None,
+                    help="with --accum-in-place: clip the gradient to this global 2-norm, computed over the accumulators")
     args = ap.parse_args()
     if args.accum_in_place and args.accum <= 0:
         ap.error("--accum-in-place goes with --accum N")
+    if args.clip_norm is not None and not args.accum_in_place:
+        ap.error("--clip-norm goes with --accum-in-place (torch's clip_grad_norm_ serves local gradients)")
     on_gpu = args.gpu is not None
     dev = f"cuda:{args.gpu}" if on_gpu else "cpu"
     dtype = torch.bfloat16 if args.bf16 else torch.float32
@@ -50,7 +57,8 @@ def main():
         with api.Client(daemon_rank=0, gpu=args.gpu, ns=mesh.ns) as c:
             opt = OffloadedAdam(model.parameters(), c, lr=3e-3)
             tiers = sorted({e["tier"] for e in opt.allocs[0].remote_info()["extents"]})
-            first = last = None
+            first = last = norm = None
+            clipped = 0
             params = list(model.parameters())
             acc = OffloadedGradAccumulator(params, c, readback=not args.accum_in_place) if args.accum > 0 else None
 
@@ -71,7 +79,10 @@ def main():
                         loss.backward()
                         acc.add(scale=1.0 / args.accum)  # remote fp32 += grad / N, one launch
                         total += loss.item()
-                    if args.accum_in_place:
+                    if args.clip_norm is not None:
+                        norm = opt.step(accumulator=acc, max_norm=args.clip_norm, skip_nonfinite=True)
+                        clipped += norm > args.clip_norm
+                    elif args.accum_in_place:
                         opt.step(accumulator=acc)  # g = the fp32 accumulators, zeroed by the same kernel
                     else:
                         sums = acc.read()
@@ -95,6 +106,8 @@ def main():
     where = "+".join({1: "host tier", 2: "peer HBM"}[t] for t in tiers)
     print(f"{args.steps} steps, mode={opt.mode}, {dtype}, optimizer state in {where}: "
           f"loss {first:.4f} -> {last:.4f}")
+    if args.clip_norm is not None:
+        print(f"clip-norm {args.clip_norm:g}: last gradient norm {norm:.4f}, {clipped} of {args.steps} steps clipped")
     if not last < 0.5 * first:
         raise SystemExit("loss did not go down")
 

@@ -268,6 +268,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_x_adam_multi_acc": (i32, [vp, vp, i32, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                            ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                            ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_uint32, i32, vp]),
+            "ocm_x_acc_sumsq": (i32, [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp, vp, u64, vp]),
+            "ocm_x_acc_sumsq_work_bytes": (u64, [i32]),
+            "ocm_x_clip_scale": (ctypes.c_double, [ctypes.c_double, ctypes.c_double, ctypes.c_double]),
             "ocm_x_set_tuning": (None, [i32, i32, i32]),
             "ocm_x_set_tuning_dir": (i32, [i32, i32, i32, i32]),
             "ocm_x_batch": (i32, [i32, vp, ctypes.POINTER(vp), i32, u64, ctypes.POINTER(u64), i32, i32]),
@@ -302,6 +305,14 @@ def _adam_hp(hp) -> tuple:
     if len(hp) == 6:
         hp += (float("nan"),)
     return hp + (1.0 - hp[0], 1.0 - hp[1])
+
+
+def clip_scale(sumsq_total: float, scale: float, max_norm: float) -> float:
+    """The gradient scale of a step clipped to ``max_norm`` (ocm/acc_norm.h, computed in double):
+    the gradient is scale * acc, its norm |scale| * sqrt(sumsq_total), and the result
+    scale * min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s rule. It is rounded
+    to fp32 once, where it becomes the fused Adam's gscale. A NaN norm gives NaN."""
+    return float(load().ocm_x_clip_scale(float(sumsq_total), float(scale), float(max_norm)))
 
 
 def last_error() -> str:
@@ -1081,6 +1092,37 @@ class Allocation:
             float(gscale), OCM_ADAM_ACC_ZERO if zero else 0, 1 if bf16 else 0, self._stream_handle(stream))
         if rc != 0:
             raise OcmError("ocm_x_adam_multi_acc: " + last_error())
+
+    def acc_sumsq(self, g_offs, ns, stream=None):
+        """ocm_x_acc_sumsq: one read-only pass over fp32 accumulators in this allocation's remote
+        half, tensor i being ns[i] words at byte offset g_offs[i] (16-byte aligned). Returns two
+        device tensors of count + 1 elements, (float64 sums of squares accumulated in fp64, int64
+        counts of inf / NaN words), the totals over all tensors last. Queued on `stream` (default:
+        torch's current stream) behind the async ops queued on this allocation; no host wait, so
+        read the results after a synchronise. Outputs and workspace are torch's."""
+        import torch
+
+        k = len(g_offs)
+        if self._c.device < 0:  # the hook's own refusal, before torch is asked for device memory
+            raise OcmError("ocm_x_acc_sumsq needs a GPU")
+        dev = torch.device("cuda", self._c.device)
+        sumsq = torch.empty(k + 1, dtype=torch.float64, device=dev)
+        bad = torch.empty(k + 1, dtype=torch.int64, device=dev)
+        work = torch.empty(int(self._c.lib.ocm_x_acc_sumsq_work_bytes(k)), dtype=torch.uint8, device=dev)
+        self._acc_sumsq_into(g_offs, ns, sumsq, bad, work, stream)
+        return sumsq, bad
+
+    def _acc_sumsq_into(self, g_offs, ns, sumsq, bad, work, stream=None) -> None:
+        """acc_sumsq into the caller's tensors (count + 1 float64, count + 1 int64, uint8 workspace)."""
+        k = len(g_offs)
+        if len(ns) != k:
+            raise OcmError(f"ocm_x_acc_sumsq: {k} offsets for {len(ns)} lengths")
+        arr_u = ctypes.c_uint64 * k
+        rc = self._c.lib.ocm_x_acc_sumsq(self.handle, k, arr_u(*ns), arr_u(*g_offs), ctypes.c_void_p(sumsq.data_ptr()),
+                                         ctypes.c_void_p(bad.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+                                         work.numel(), self._stream_handle(stream))
+        if rc != 0:
+            raise OcmError("ocm_x_acc_sumsq: " + last_error())
 
     def time_onesided(self, op_flag: int, nbytes: int, iters: int, local_offset: int = 0, remote_offset: int = 0) -> float:
         """Seconds per blocking one-sided op, timed inside the native library."""

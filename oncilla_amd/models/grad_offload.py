@@ -23,12 +23,17 @@ one chunk of zeros of at most 4 MiB::
 reads the accumulators where they are and zeroes them in the same pass, so ``zero()`` (one
 batch of puts from the chunk) runs only when the accumulator is built.
 
+``sumsq()`` / ``grad_norm()`` reduce the accumulators where they live (one read-only kernel pass:
+per-parameter fp64 sums of squares and counts of inf / NaN words), with ``readback`` either way:
+what gradient clipping and loss scaling need, without the read-back region.
+
 Streams: ``add`` waits for work already queued on torch's current stream (the backward
 that wrote the gradients), and after an async ``add`` that stream waits for the
 accumulate before anything overwrites them (``zero_grads``, the next backward).
 """
 from __future__ import annotations
 
+import math
 from typing import Iterable
 
 import numpy as np
@@ -122,6 +127,25 @@ class OffloadedGradAccumulator:
         self.alloc.stream_wait()  # earlier readers of the region on torch's stream
         self.alloc.get(self.grad_bytes, 0, 4 * self.total_elems)
         return [self._readback[e: e + n].view(p.shape) for p, e, _, n in self._slots]
+
+    def sumsq(self, stream=None):
+        """(float64[count + 1], int64[count + 1]) device tensors: per parameter the sum of squares
+        of its accumulators (fp64 accumulation) and the number of inf / NaN words among them, the
+        totals last; one read-only pass where the accumulators live (Allocation.acc_sumsq over the
+        true element counts, not the padded ones). Queued behind the accumulates; no host wait.
+        Works with ``readback`` either way."""
+        return self.alloc.acc_sumsq([4 * e for _, e, _, _ in self._slots], [n for _, _, _, n in self._slots], stream=stream)
+
+    def _norm_parts(self) -> tuple:
+        """(total sum of squares, total non-finite count) as Python numbers: one host synchronise."""
+        sumsq, bad = self.sumsq()
+        return float(sumsq[-1].item()), int(bad[-1].item())  # .item() waits for the stream
+
+    def grad_norm(self, scale: float = 1.0) -> tuple:
+        """(norm, nonfinite): the 2-norm of scale * every accumulator, a Python float, and how many
+        accumulator words are inf or NaN. One host synchronise (the results are read back)."""
+        total, bad = self._norm_parts()
+        return abs(scale) * math.sqrt(total), bad
 
     def zero(self) -> None:
         """Reset every accumulator to +0."""

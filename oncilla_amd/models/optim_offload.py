@@ -35,6 +35,12 @@ store +0 back over them (ocm_x_adam_multi_acc). No fp32 gradient copy in local H
 read-back, no separate zeroing pass; for bfloat16 parameters the gradient reaches the fp32
 master update unrounded.
 
+step(accumulator=acc, max_norm=X, skip_nonfinite=True) makes that path usable with gradient
+clipping and loss scaling: one read-only reduction over the accumulators where they live
+(ocm_x_acc_sumsq: fp64 sum of squares, count of inf / NaN words), one host synchronise, and the
+clip coefficient goes into the scale the update kernel already takes; an overflowed step is
+skipped before anything reaches the moments.
+
 The update is torch.optim.Adam's (L2 weight decay, bias correction; reference
 behaviour: torch/optim/adam.py single-tensor path), so results match it to
 float32 rounding (tests/test_optim_offload.py). The reference runtime has no
@@ -164,13 +170,17 @@ class OffloadedAdam:
         # every parameter in ceil(n / 32) launches (descriptors in the kernel arguments)
         self.allocs[0].adam_multi(ps, gs, mo, vo, hp, w_offs=wo if self.bf16 else None)
 
-    def _step_accumulator(self, accumulator, scale: float, zero: bool) -> None:
-        """Every parameter's gradient is scale * its fp32 accumulator slot, read (and zeroed) in
-        place by the update kernel; .grad is not consulted."""
+    def _slots_of(self, accumulator) -> list:
         slots = accumulator._slots
         if len(slots) != len(self.params) or any(s[0] is not p for s, p in zip(slots, self.params)):
             raise ValueError("the accumulator's parameter list is not this optimizer's, in order")
-        ps = [p.data for p in self.params]
+        return slots
+
+    def _step_accumulator(self, accumulator, scale: float, zero: bool) -> None:
+        """Every parameter's gradient is scale * its fp32 accumulator slot, read (and zeroed) in
+        place by the update kernel; .grad is not consulted."""
+        slots = self._slots_of(accumulator)
+        ps =[p.data for p in self.params]
         mo = [4 * s for s in self.starts]
         vo = [4 * (self.padded + s) for s in self.starts]
         wo = [4 * (2 * self.padded + s) for s in self.starts] if self.bf16 else None
@@ -211,22 +221,45 @@ class OffloadedAdam:
             denom = (v.sqrt() / math.sqrt(bc2)).add_(self.eps)
             pv.addcdiv_(m, denom, value=-step_size)
 
-    def step(self, accumulator=None, scale: float = 1.0, zero: bool = True) -> None:
+    def step(self, accumulator=None, scale: float = 1.0, zero: bool = True, max_norm=None, skip_nonfinite: bool = False):
         """One Adam step over every parameter; queued on torch's current stream (GPU) without a host wait.
 
         accumulator: an OffloadedGradAccumulator over this optimizer's parameters, in order (fused
         mode only). The gradients are then scale * its fp32 accumulators, read from remote memory
-        by the update kernel itself and, with `zero`, reset to +0 in the same pass."""
+        by the update kernel itself and, with `zero`, reset to +0 in the same pass.
+
+        max_norm / skip_nonfinite (with an accumulator only; torch's clip_grad_norm_ serves local
+        gradients): one read-only pass over the accumulators first (accumulator.sumsq()) and ONE
+        host synchronise to read its two totals. With max_norm the gradients are clipped to that
+        global 2-norm: the kernel's scale becomes api.clip_scale(sum of squares, scale, max_norm).
+        With skip_nonfinite, a step whose accumulators hold an inf or NaN runs no update kernel and
+        does not count: the accumulators are reset to +0 (accumulator.zero()) and everything else
+        stays as it is. Either way the total norm of scale * accumulators, a Python float, is
+        returned (non-finite for a skipped step); None when neither argument is given."""
+        checked = max_norm is not None or skip_nonfinite
+        if checked and accumulator is None:
+            raise ValueError("max_norm / skip_nonfinite read the gradients from an accumulator; "
+                             "torch.nn.utils.clip_grad_norm_ serves local gradients")
         if accumulator is not None:
             if self.mode != "fused":
                 raise ValueError("step(accumulator=...) needs mode='fused'")
+            norm = None
+            if checked:
+                self._slots_of(accumulator)  # another list is refused before its accumulators are touched
+                total, bad = accumulator._norm_parts()
+                norm = abs(scale) * math.sqrt(total)
+                if skip_nonfinite and bad:
+                    accumulator.zero()
+                    return norm
+                if max_norm is not None:
+                    scale = api.clip_scale(total, scale, max_norm)
             self.t += 1
             try:
                 self._step_accumulator(accumulator, scale, zero)
             except Exception:
                 self.t -= 1  # nothing ran: every tensor is checked before the first launch
                 raise
-            return
+            return norm
         self.t += 1
         if self.mode == "fused":
             self._step_fused()
