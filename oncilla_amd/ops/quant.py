@@ -18,6 +18,12 @@ Per group of 32 consecutive elements, widened exactly to fp32:
 Decoding gives ``float(code) * 2**e`` in fp32, rounded to nearest even into the
 element type. A record is the codes followed by the scale bytes.
 
+A get decodes whatever record it finds, one of another producer too: every code under
+every scale byte 0..255 decodes by the line above (scale byte 255 is ``e = 128``:
+infinities, and zero for the zero codes; scale byte 0 gives fp32 subnormal products,
+rounded once). A NaN code (``0x7f``, ``0xff``) decodes to some NaN of the element type;
+the payload is not specified.
+
 The MXFP4 format (``OCM_QUANT_MXFP4``, the ``mx4_*`` functions; host codec
 ``csrc/include/ocm/mx4.h``) differs in the code alone. Per group of 32 elements:
 
@@ -28,6 +34,11 @@ The MXFP4 format (``OCM_QUANT_MXFP4``, the ``mx4_*`` functions; host codec
    ``-0`` (as everything that rounds to zero from below) keeps its sign.
 3. Decoding gives ``value(code) * 2**e`` in fp32 (exact), rounded to nearest even into the
    element type: fp16 overflows to infinity and underflows through its subnormals.
+   This holds for every code byte under every scale byte 0..254. Scale byte 255 is E8M0's
+   NaN: it is never written, and what it decodes to is not specified for MXFP4 (the gfx950
+   fp4 converts take the scale as the exponent field of an operand; this function gives
+   ``value(code) * 2**128``). Observed once on an MI355X, as a record and no promise: the
+   kernel returned a NaN for every code, zero codes included (bf16 ``0xffc0``, fp16 ``0xfe00``).
 
 An MXFP4 record of n elements is n / 2 code bytes (element 2i in the low nibble of byte i,
 element 2i + 1 in the high nibble), then n / 32 scale bytes.

@@ -1,5 +1,5 @@
 """Cases shared by the MXFP4 tests (test_mx4_cpu.py, test_gpu_mx4.py): the edge groups, the
-all-patterns sweep, the mixed-format list and a strided layout. Everything is compared byte
+all-patterns sweep, the decode table, the mixed-format list and a strided layout. Everything is compared byte
 for byte with the torch oracle (oncilla_amd.ops.mx4_*_reference). The byte movers are those
 of quant_cases.py."""
 import functools
@@ -11,7 +11,8 @@ import torch
 from oncilla_amd import api
 from oncilla_amd.ops import (mx4_decode_reference, mx4_encode_reference, mx4_record_reference, mx4_rows_reference,
                              mx8_record_reference)
-from quant_cases import UNIT, _bits, _vals, random_elems, read_local, read_remote, write_local, write_remote
+from quant_cases import (UNIT, DecodeTable, _bits, _vals, all_patterns, random_elems, read_local, read_remote, write_local,
+                         write_remote)
 from quant_cases import roundtrip as roundtrip8
 
 DTYPES = [torch.bfloat16, torch.float16]
@@ -58,14 +59,23 @@ def sweep(dtype):
     (a group spans every binade and both signs: most of it rounds to zero). Inf and NaN patterns
     are replaced by zero. Returns (elements, record, decoded) with the oracle's results, computed
     once per dtype and shared: treat them as read-only."""
-    p = torch.arange(65536, dtype=torch.int32)
-    both = torch.cat([p, p.view(32, 2048).t().reshape(-1)])
-    exp_all_ones = (both & 0x7F80) == 0x7F80 if dtype == torch.bfloat16 else (both & 0x7C00) == 0x7C00
-    both = torch.where(exp_all_ones, torch.zeros_like(both), both)
-    x = both.to(torch.int16).view(dtype)
-    assert torch.isfinite(x.float()).all()
+    x = all_patterns(dtype)
     codes, scales = mx4_encode_reference(x)
     return x, torch.cat([codes, scales]), mx4_decode_reference(codes, scales, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def decode_table():
+    """65280 code bytes, byte[i] = i & 255, under 4080 scale bytes, scale[g] = g // 16: every code
+    byte (both nibbles, every pairing) meets every scale byte 0..254, 130560 elements. Scale
+    byte 255 is E8M0's NaN: no encoder writes it and its decode is not specified."""
+    codes = (torch.arange(255 * 256, dtype=torch.int32) & 255).to(torch.uint8)
+    scales = (torch.arange(255 * 16, dtype=torch.int32) // 16).to(torch.uint8)
+    assert int(scales.max()) == 254 and int(torch.bincount(scales.long()).min()) == 16
+    return DecodeTable("mxfp4", codes, scales, mx4_decode_reference)
+
+
+TABLE_ROWS = 30  # the table as rows of 4352 elements: two tiles and eight groups each
 
 
 def roundtrip(x):

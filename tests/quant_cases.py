@@ -1,6 +1,9 @@
 """Cases shared by the converting-transfer tests (test_quant_cpu.py, test_gpu_quant.py):
-the edge groups, the 60-op list, and helpers that move raw bytes through an allocation.
-Everything is compared byte for byte with the torch oracle (oncilla_amd.ops.quant)."""
+the edge groups, the all-patterns sweep, the decode table (every code under every scale
+byte), the non-finite groups, the 60-op list, and helpers that move raw bytes through an
+allocation. Everything is compared byte for byte with the torch oracle
+(oncilla_amd.ops.quant); the one allowance is the payload of a NaN that a NaN code decodes to."""
+import functools
 import random
 
 import numpy as np
@@ -95,6 +98,232 @@ def write_remote(a, stage, roff, t):
 def read_remote(a, stage, roff, n):
     a.get(stage, roff, n)
     return read_local(a, stage, n)
+
+
+def _up(x, m):
+    return (x + m - 1) // m * m
+
+
+def mismatches(got, want, show=int, where=None):
+    """(count, the first dozen (index, got, want)) of the elements that differ, of those that
+    `where` selects if it is given."""
+    bad = got != want
+    if where is not None:
+        bad &= where
+    bad = bad.nonzero().reshape(-1)
+    return bad.numel(), [(int(i), show(got[i]), show(want[i])) for i in bad[:12]]
+
+
+def hex16(v):
+    return hex(int(v) & 0xFFFF)
+
+
+# ---- the all-patterns sweep ----
+
+def all_patterns(dtype):
+    """Every 16-bit pattern of `dtype`, twice, 131072 elements in 4096 groups: once in pattern
+    order (a group holds 32 neighbouring values: codes near the top of the range) and once dealt
+    out 2048 apart (a group spans every binade and both signs: most of it rounds to zero). Inf
+    and NaN patterns are replaced by zero."""
+    p = torch.arange(65536, dtype=torch.int32)
+    both = torch.cat([p, p.view(32, 2048).t().reshape(-1)])
+    exp_all_ones = (both & 0x7F80) == 0x7F80 if dtype == torch.bfloat16 else (both & 0x7C00) == 0x7C00
+    both = torch.where(exp_all_ones, torch.zeros_like(both), both)
+    x = both.to(torch.int16).view(dtype)
+    assert torch.isfinite(x.float()).all()
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def sweep(dtype):
+    """all_patterns(dtype) with the oracle's MXFP8 results: (elements, record, decoded), computed
+    once per dtype and shared: treat them as read-only."""
+    x = all_patterns(dtype)
+    codes, scales = mx8_encode_reference(x)
+    return x, torch.cat([codes, scales]), mx8_decode_reference(codes, scales, dtype)
+
+
+def run_sweep(a, dtype):
+    """One put of the whole sweep at remote offset UNIT - 64 (codes and scale bytes cross stripe
+    units), the record against the oracle's; one get back into a range filled with 0x5A5A, the
+    elements against the oracle's decode. Needs sweep_bytes() in the pair."""
+    x, record, decoded = sweep(dtype)
+    n = x.numel()
+    write_local(a, 0, x)
+    a.quant_batch(np.array([[1, 0, UNIT - 64, n]]), dtype)
+    got = read_remote(a, 2 * n, UNIT - 64, record.numel())
+    count, first = mismatches(got, record)
+    assert count == 0, ("record", count, first)
+    write_local(a, 0, torch.full((n,), 0x5A5A, dtype=torch.int16))
+    a.quant_batch(np.array([[0, 0, UNIT - 64, n]]), dtype)
+    got = read_local(a, 0, 2 * n).view(torch.int16)
+    count, first = mismatches(got, decoded.view(torch.int16), hex16)
+    assert count == 0, ("decoded", count, first)
+
+
+def sweep_bytes():
+    """(local_bytes, remote_bytes) of the pair run_sweep needs: the elements and a staging range
+    for the record behind them; the record from UNIT - 64."""
+    n, rec = 131072, api.quant_bytes(131072)
+    return 2 * n + _up(rec, UNIT), _up(UNIT + rec, UNIT)
+
+
+# ---- decode tables: every code under every scale byte ----
+
+class DecodeTable:
+    """A record that no encoder wrote: `codes` and `scales` (uint8) as they are, 32 elements per
+    scale byte, decoded by one converting get and compared bit for bit with `decode` (the
+    oracle). `nan` marks the elements whose code is a NaN code, if the format has any: those
+    decode to some NaN of the element type, the payload is not specified, and everything else
+    is exact."""
+
+    def __init__(self, fmt, codes, scales, decode, nan=None):
+        self.fmt, self.codes, self.scales, self._decode, self.nan = fmt, codes, scales, decode, nan
+        self.elems = 32 * scales.numel()
+        assert api.quant_bytes(self.elems, fmt) == codes.numel() + scales.numel()
+        self._want = {}
+
+    def record(self):
+        return torch.cat([self.codes, self.scales])
+
+    def row_records(self, rows):
+        """The table as `rows` records of elems / rows elements each: [rows, record bytes], row
+        r holding its share of the codes, then its share of the scale bytes."""
+        assert self.elems % (32 * rows) == 0
+        return torch.cat([self.codes.view(rows, -1), self.scales.view(rows, -1)], dim=1)
+
+    def want(self, dtype):
+        """The oracle's decode as int16, computed once per dtype: treat it as read-only. Its rows
+        are the decodes of row_records(), a row being whole groups."""
+        if dtype not in self._want:
+            self._want[dtype] = self._decode(self.codes, self.scales, dtype).view(torch.int16)
+        return self._want[dtype]
+
+    def check(self, got, dtype):
+        """got: the decoded elements as int16."""
+        want = self.want(dtype)
+        exact = None
+        if self.nan is not None:
+            assert torch.isnan(want.view(dtype)[self.nan].float()).all()  # the oracle's are NaNs too
+            not_nan = (~torch.isnan(got.view(dtype).float())) & self.nan
+            assert not not_nan.any(), ("NaN codes that decoded to a number", int(not_nan.sum()),
+                                       [(int(i), hex16(got[i])) for i in not_nan.nonzero().reshape(-1)[:12]])
+            exact = ~self.nan
+        count, first = mismatches(got, want, hex16, exact)
+        assert count == 0, (self.fmt, count, first)
+
+    def bytes(self, rows=1):
+        """(local_bytes, remote_bytes) of the pair run() or run_strided(rows) needs."""
+        ls, rs = self._strides(rows)
+        return _up(rows * ls + rows * rs, UNIT), _up(UNIT + rows * rs, UNIT)
+
+    def _strides(self, rows):
+        if rows == 1:
+            return 2 * self.elems, _up(self.codes.numel() + self.scales.numel(), 32)
+        return 2 * self.elems // rows + 16, _up(api.quant_bytes(self.elems // rows, self.fmt), 32) + 32
+
+    def run(self, a, dtype):
+        """The record raw into the remote half at UNIT - 64 with a plain put, one converting get
+        into a range filled with 0x5A5A."""
+        n = self.elems
+        write_remote(a, 2 * n, UNIT - 64, self.record())
+        write_local(a, 0, torch.full((n,), 0x5A5A, dtype=torch.int16))
+        a.quant_batch(np.array([[0, 0, UNIT - 64, n]]), dtype, format=self.fmt)
+        self.check(read_local(a, 0, 2 * n).view(torch.int16), dtype)
+
+    def run_strided(self, a, dtype, rows):
+        """The same values through the strided op: the table as `rows` records, a remote stride
+        of the rounded record plus 32 and a local one of the row plus 16, one strided converting
+        get into a range filled with 0x5A; the bytes between the decoded rows keep the fill."""
+        re = self.elems // rows
+        ls, rs = self._strides(rows)
+        recs = torch.full((rows, rs), 0xA5, dtype=torch.uint8)
+        rr = self.row_records(rows)
+        recs[:, :rr.shape[1]] = rr
+        write_remote(a, rows * ls, UNIT - 64, recs)
+        write_local(a, 0, torch.full((rows * ls,), 0x5A, dtype=torch.uint8))
+        a.quant_strided_batch(np.array([[0, 0, UNIT - 64, re, rows, ls, rs]]), dtype, format=self.fmt)
+        got = read_local(a, 0, rows * ls).view(rows, ls)
+        assert (got[:, 2 * re:] == 0x5A).all(), "the bytes behind a decoded row"
+        self.check(got[:, :2 * re].contiguous().view(torch.int16).reshape(-1), dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def decode_table():
+    """MXFP8: 65536 codes, code[i] = i & 255, under 2048 scale bytes, scale[g] = g // 8: every
+    scale byte 0..255 meets every code, scale byte 255 (float(code) * 2^128: infinities, zero
+    for the zero codes) and 0 (fp32 subnormal products) included. The 512 elements whose code
+    is 0x7f or 0xff decode to some NaN."""
+    codes = (torch.arange(65536, dtype=torch.int32) & 255).to(torch.uint8)
+    scales = (torch.arange(2048, dtype=torch.int32) // 8).to(torch.uint8)
+    nan = (codes & 0x7F) == 0x7F
+    assert int(nan.sum()) == 512  # the NaN allowance covers these and nothing else
+    return DecodeTable("mxfp8", codes, scales, mx8_decode_reference, nan)
+
+
+TABLE_ROWS = 32  # the MXFP8 table as rows of 2048 elements: one tile each
+
+
+# ---- non-finite groups ----
+
+N_NONFINITE = 2048 + 64  # one tile and two groups: both MXFP8 rounds and a second tile take part
+# (group, element of the group, value): group 3 is lanes 6 and 7 of the MXFP8 tile and the element
+# sits in the odd lane, whose maximum reaches lane 6 by the shuffle; group 40 is in the second
+# MXFP8 round; group 65 is the last one, in the second tile
+NONFINITE = ((3, 21, float("inf")), (40, 5, float("nan")), (65, 31, float("-inf")))
+
+
+def run_nonfinite_put(a, dtype, fmt, record_reference):
+    """A put of random elements with an Inf, a NaN and a -Inf in three groups: every code and scale
+    byte of every other group equals the oracle record of the same input with those three groups
+    zeroed, and 32 sentinel bytes before and after the record are intact. The three groups' own
+    bytes are not compared (their codes are unspecified). Needs 16384 local and 4 * UNIT remote bytes."""
+    n, ng = N_NONFINITE, N_NONFINITE // 32
+    x = random_elems(n, dtype, seed=77)
+    clean = x.clone()
+    for g, k, v in NONFINITE:
+        x[32 * g + k] = v
+        clean[32 * g:32 * g + 32] = 0
+    assert int((~torch.isfinite(x.float())).sum()) == 3 and torch.isfinite(clean.float()).all()
+    want = record_reference(clean)
+    rb = api.quant_bytes(n, fmt)
+    per = (rb - ng) // ng  # code bytes of a group
+    compared = torch.ones(rb, dtype=torch.bool)
+    for g, _, _ in NONFINITE:
+        compared[per * g:per * g + per] = False
+        compared[rb - ng + g] = False
+    assert int(compared.sum()) == rb - 3 * (per + 1)
+    stage, ro = 8192, UNIT - 64
+    fill = torch.full((32,), 0xA5, dtype=torch.uint8)
+    write_remote(a, stage, ro - 32, torch.full((rb + 64,), 0xA5, dtype=torch.uint8))
+    write_local(a, 0, x)
+    a.quant_batch(np.array([[1, 0, ro, n]]), dtype, format=fmt)
+    got = read_remote(a, stage, ro - 32, rb + 64)
+    assert torch.equal(got[:32], fill) and torch.equal(got[-32:], fill), "the bytes around the record"
+    count, first = mismatches(got[32:-32], want, int, compared)
+    assert count == 0, (fmt, count, first)
+
+
+def run_nan_codes_get(a, dtype):
+    """The get direction, MXFP8: the oracle record of a finite input with three codes overwritten
+    by the NaN codes 0x7f / 0xff, in the groups of NONFINITE. Those three elements decode to a
+    NaN; every other element equals the oracle decode exactly."""
+    n = N_NONFINITE
+    x = random_elems(n, dtype, seed=78)
+    record = mx8_record_reference(x)
+    want = roundtrip(x).view(torch.int16)
+    at = torch.zeros(n, dtype=torch.bool)
+    for (g, k, _), code in zip(NONFINITE, (0x7F, 0xFF, 0x7F)):
+        record[32 * g + k] = code
+        at[32 * g + k] = True
+    stage, ro = 8192, UNIT - 64
+    write_remote(a, stage, ro, record)
+    write_local(a, 0, torch.full((n,), 0x5A5A, dtype=torch.int16))
+    a.quant_batch(np.array([[0, 0, ro, n]]), dtype)
+    got = read_local(a, 0, 2 * n).view(torch.int16)
+    assert torch.isnan(got.view(dtype)[at].float()).all(), [hex16(v) for v in got[at]]
+    count, first = mismatches(got, want, hex16, ~at)
+    assert count == 0, (count, first)
 
 
 # ---- the 60-op list ----

@@ -6,11 +6,12 @@ import numpy as np
 import pytest
 import torch
 
-from mx4_cases import DTYPES, MixedList, edge_groups, exercise_kv, roundtrip, run_strided, sweep, up32
+from mx4_cases import (DTYPES, TABLE_ROWS, MixedList, decode_table, edge_groups, exercise_kv, roundtrip, run_strided, sweep,
+                       up32)
 from oncilla_amd import api
 from oncilla_amd.models import PagedKVOffload
 from oncilla_amd.ops import mx4_record_reference
-from quant_cases import UNIT, random_elems, read_local, read_remote, write_local, write_remote
+from quant_cases import UNIT, random_elems, read_local, read_remote, run_nonfinite_put, write_local, write_remote
 
 pytestmark = pytest.mark.gpu
 
@@ -79,6 +80,28 @@ def test_all_patterns_sweep(mesh_factory, n_daemons, dtype):
         want = decoded.view(torch.int16)
         bad = (got != want).nonzero().reshape(-1)
         assert bad.numel() == 0, (bad.numel(), [(int(i), hex(int(got[i]) & 0xFFFF), hex(int(want[i]) & 0xFFFF)) for i in bad[:12]])
+        a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_decode_table(mesh_factory, n_daemons, dtype):
+    # records no encoder wrote: every code byte under every scale byte 0..254 through get_tile_mx4
+    # (the nibble-to-lane mapping, the scale operand of the packed converts at both ends)
+    t = decode_table()
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, *t.bytes(), n_daemons)
+        t.run(a, dtype)
+        a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_nonfinite_groups_stay_contained(mesh_factory, n_daemons, dtype):
+    # the put direction alone: E2M1 has no NaN code, and scale byte 255 is not specified
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, 16384, 4 * UNIT, n_daemons)
+        run_nonfinite_put(a, dtype, "mxfp4", mx4_record_reference)
         a.free()
 
 
@@ -177,6 +200,17 @@ def test_strided_rows(mesh_factory, n_daemons, rows, row_elems, extra_stride):
         after = api.quant_strided_counters()
         assert after["n_quant_strided"] == before["n_quant_strided"] + 2
         assert after["bytes_quant_strided_wire"] == before["bytes_quant_strided_wire"] + 2 * rows * api.quant_bytes(row_elems, "mxfp4")
+        a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_decode_table_rows(mesh_factory, n_daemons, dtype):
+    # the decode table through the strided kernel's own tile location: 30 rows of 4352 elements
+    t = decode_table()
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, *t.bytes(TABLE_ROWS), n_daemons)
+        t.run_strided(a, dtype, TABLE_ROWS)
         a.free()
 
 

@@ -8,8 +8,8 @@ import torch
 from oncilla_amd import api
 from oncilla_amd.models import PagedKVOffload
 from oncilla_amd.ops import mx8_decode_reference, mx8_encode_reference, mx8_record_reference
-from quant_cases import (UNIT, OpList, edge_groups, exercise_kv, random_elems, read_local, read_remote, roundtrip,
-                         write_local, write_remote)
+from quant_cases import (UNIT, OpList, decode_table, edge_groups, exercise_kv, random_elems, read_local, read_remote,
+                         roundtrip, run_nan_codes_get, run_nonfinite_put, run_sweep, sweep_bytes, write_local, write_remote)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +49,38 @@ def test_edge_groups(mesh_factory, n_daemons, dtype):
         for k, (name, x) in enumerate(groups.items()):
             got = read_local(a, 4096 + 64 * k, 64).view(torch.int16)
             assert torch.equal(got, roundtrip(x).view(torch.int16)), (name, got.tolist())
+        a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_all_patterns_sweep(mesh_factory, n_daemons, dtype):
+    # every finite 16-bit pattern through put_tile's multiply, clamp and packed convert, and back
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, *sweep_bytes())
+        run_sweep(a, dtype)
+        a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_decode_table(mesh_factory, n_daemons, dtype):
+    # records no encoder wrote: every code under every scale byte through get_tile (ldexpf into fp32
+    # subnormals and past the fp32 range, the narrowing of both, the NaN codes)
+    t = decode_table()
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, *t.bytes())
+        t.run(a, dtype)
+        a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_nonfinite_groups_stay_contained(mesh_factory, n_daemons, dtype):
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, 16384, 4 * UNIT)
+        run_nonfinite_put(a, dtype, "mxfp8", mx8_record_reference)
+        run_nan_codes_get(a, dtype)
         a.free()
 
 

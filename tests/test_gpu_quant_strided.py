@@ -9,7 +9,7 @@ import torch
 from oncilla_amd import api
 from oncilla_amd.models import PagedKVOffload
 from oncilla_amd.ops import mx8_rows_reference
-from quant_cases import UNIT, random_elems, read_local, roundtrip, write_local, write_remote
+from quant_cases import TABLE_ROWS, UNIT, decode_table, random_elems, read_local, roundtrip, write_local, write_remote
 from quant_strided_cases import (DTYPES, ROWS, STRIDES, Case, edge_case, exercise_layered_quant_kv, expand, halves,
                                  list_case, load_pair, record_up32, run_case, src_wire_bytes)
 
@@ -45,6 +45,18 @@ def test_edge_rows(mesh_factory, n_daemons, rows):
             assert after["bytes_quant_strided_src"] == before["bytes_quant_strided_src"] + src
             assert after["bytes_quant_strided_wire"] == before["bytes_quant_strided_wire"] + wire
             a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n_daemons", N_DAEMONS)
+def test_decode_table_rows(mesh_factory, n_daemons, dtype):
+    # every code under every scale byte through the strided kernel's own tile location: 32 rows of
+    # 2048 elements, one strided get
+    t = decode_table()
+    with _client(mesh_factory, n_daemons) as c:
+        a = _pair(c, *t.bytes(TABLE_ROWS), n_daemons)
+        t.run_strided(a, dtype, TABLE_ROWS)
+        a.free()
 
 
 @pytest.mark.parametrize("n_daemons", N_DAEMONS)

@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 import torch
 
-from mx4_cases import (DTYPES, MixedList, edge_groups, exercise_kv, roundtrip, run_strided, sweep, up32)
+from mx4_cases import (DTYPES, TABLE_ROWS, MixedList, decode_table, edge_groups, exercise_kv, roundtrip, run_strided, sweep,
+                       up32)
 from oncilla_amd import api
 from oncilla_amd.models import PagedKVOffload
 from oncilla_amd.ops import mx4_decode_reference, mx4_encode_reference, mx4_record_reference, mx4_rows_reference
-from quant_cases import UNIT, random_elems, read_local, read_remote, write_local, write_remote
+from quant_cases import UNIT, random_elems, read_local, read_remote, run_nonfinite_put, write_local, write_remote
 
 VALUES = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=torch.float64)
 
@@ -130,6 +131,26 @@ def test_all_patterns_sweep(client, dtype):
     assert torch.equal(read_remote(a, 2 * n, UNIT - 64, record.numel()), record)
     a.quant_batch(np.array([[0, 0, UNIT - 64, n]]), dtype, format="mxfp4")
     assert torch.equal(read_local(a, 0, 2 * n).view(torch.int16), decoded.view(torch.int16))
+    a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_decode_table(client, dtype):
+    t = decode_table()
+    assert t.elems == 130560 and t.codes.numel() == 65280 and t.scales.numel() == 4080
+    a = _pair(client, *t.bytes())
+    t.run(a, dtype)
+    a.free()
+    a = _pair(client, *t.bytes(TABLE_ROWS))
+    t.run_strided(a, dtype, TABLE_ROWS)
+    a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_nonfinite_groups_stay_contained(client, dtype):
+    # the put direction alone: E2M1 has no NaN code, and scale byte 255 is not specified
+    a = _pair(client, 16384, 4 * UNIT)
+    run_nonfinite_put(a, dtype, "mxfp4", mx4_record_reference)
     a.free()
 
 

@@ -10,7 +10,8 @@ import torch
 from oncilla_amd import api
 from oncilla_amd.models import PagedKVOffload
 from oncilla_amd.ops import mx8_decode_reference, mx8_encode_reference, mx8_record_reference
-from quant_cases import (UNIT, OpList, edge_groups, exercise_kv, random_elems, read_local, read_remote, roundtrip,
+from quant_cases import (TABLE_ROWS, UNIT, OpList, decode_table, edge_groups, exercise_kv, random_elems, read_local,
+                         read_remote, roundtrip, run_nan_codes_get, run_nonfinite_put, run_sweep, sweep, sweep_bytes,
                          write_local, write_remote)
 
 DTYPES = [torch.bfloat16, torch.float16]
@@ -81,6 +82,53 @@ def test_quant_get_of_oracle_records(client, dtype):
     write_remote(a, 2 * n, UNIT - 320, mx8_record_reference(x))  # the codes cross a unit boundary
     a.quant_batch(np.array([[0, 0, UNIT - 320, n]]), dtype)
     assert torch.equal(read_local(a, 0, 2 * n).view(torch.int16), roundtrip(x).view(torch.int16))
+    a.free()
+
+
+def test_sweep_strength():
+    """What the all-patterns sweep reaches, so that it cannot be hollowed out later: floors under
+    the measured 212 codes and 248 scale bytes (bf16) and 174 codes (fp16)."""
+    x, record, _ = sweep(torch.bfloat16)
+    n = x.numel()
+    assert n == 131072 and record.numel() == n + n // 32
+    codes, scales = record[:n].unique(), record[n:].unique()
+    print("bf16 sweep:", codes.numel(), "codes,", scales.numel(), "scale bytes")
+    assert codes.numel() >= 200 and scales.numel() >= 240 and int(scales[0]) == 0
+    x, record, _ = sweep(torch.float16)
+    codes, scales = record[:n].unique(), record[n:].unique()
+    print("fp16 sweep:", codes.numel(), "codes,", scales.numel(), "scale bytes")
+    assert codes.numel() >= 170
+    # both halves of the sweep hold every finite pattern once
+    for dtype, finite in ((torch.bfloat16, 65536 - 2 * 128), (torch.float16, 65536 - 2 * 1024)):
+        p = sweep(dtype)[0].view(torch.int16).to(torch.int32) & 0xFFFF
+        for half in (p[:65536], p[65536:]):
+            assert half.unique().numel() == finite and int((half == 0).sum()) == 65536 - finite + 1
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_all_patterns_sweep(client, dtype):
+    a = _pair(client, *sweep_bytes())
+    run_sweep(a, dtype)
+    a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_decode_table(client, dtype):
+    t = decode_table()
+    assert t.elems == 65536 and t.record().numel() == 67584 and int(t.nan.sum()) == 512
+    a = _pair(client, *t.bytes())
+    t.run(a, dtype)
+    a.free()
+    a = _pair(client, *t.bytes(TABLE_ROWS))
+    t.run_strided(a, dtype, TABLE_ROWS)
+    a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_nonfinite_groups_stay_contained(client, dtype):
+    a = _pair(client, 16384, 4 * UNIT)
+    run_nonfinite_put(a, dtype, "mxfp8", mx8_record_reference)
+    run_nan_codes_get(a, dtype)
     a.free()
 
 
