@@ -71,15 +71,17 @@ OCM_STRIDED_HD inline void strided_locate(const XferStridedOp &op, uint64_t t, u
     *k = t - *row * op.tiles_per_row;
 }
 
-// The spans of piece k of row `row`: 1, or 2 when the piece crosses a stripe-unit
-// boundary of the striped side (n_ext > 1; tile <= unit, so at most one boundary).
-OCM_STRIDED_HD inline int strided_row_pieces(const XferStridedOp &op, uint64_t row, uint64_t k, uint32_t n_ext,
-                                             uint32_t unit_shift, uint32_t tile_shift, StridedPiece out[2]) {
+// The spans of piece k of a row of row_bytes whose first byte is lin_row_off of the linear
+// buffer and rem_row_off of the striped address space: 1, or 2 when the piece crosses a
+// stripe-unit boundary of the striped side (n_ext > 1; tile <= unit, so at most one
+// boundary). The span arithmetic every row-relative kernel shares.
+OCM_STRIDED_HD inline int strided_pieces_at(uint64_t lin_row_off, uint64_t rem_row_off, uint64_t row_bytes, uint64_t k,
+                                            uint32_t n_ext, uint32_t unit_shift, uint32_t tile_shift, StridedPiece out[2]) {
     const uint64_t in_row = k << tile_shift;
-    const uint64_t left = op.row_bytes - in_row;
+    const uint64_t left = row_bytes - in_row;
     const uint64_t n = left < (1ull << tile_shift) ? left : (1ull << tile_shift);
-    const uint64_t lo = op.lin_off + row * op.lin_stride + in_row;
-    const uint64_t ro = op.rem_off + row * op.rem_stride + in_row;
+    const uint64_t lo = lin_row_off + in_row;
+    const uint64_t ro = rem_row_off + in_row;
     out[0].lin_off = lo;
     out[0].rem_off = ro;
     out[0].n = n;
@@ -95,6 +97,23 @@ OCM_STRIDED_HD inline int strided_row_pieces(const XferStridedOp &op, uint64_t r
         }
     }
     return 1;
+}
+
+// The spans of piece k of the row that is row `lin_row` of the linear side's table and row
+// `rem_row` of the striped side's. `Op`: a descriptor with lin_off, rem_off, row_bytes and
+// one stride per side (XferStridedOp; XferIndexedOp of ocm/indexed.h, whose rows are picked
+// by index arrays).
+template <class Op>
+OCM_STRIDED_HD inline int strided_row_pieces(const Op &op, uint64_t lin_row, uint64_t rem_row, uint64_t k, uint32_t n_ext,
+                                             uint32_t unit_shift, uint32_t tile_shift, StridedPiece out[2]) {
+    return strided_pieces_at(op.lin_off + lin_row * op.lin_stride, op.rem_off + rem_row * op.rem_stride, op.row_bytes, k, n_ext,
+                             unit_shift, tile_shift, out);
+}
+
+// A strided op's row is the same row on both sides.
+OCM_STRIDED_HD inline int strided_row_pieces(const XferStridedOp &op, uint64_t row, uint64_t k, uint32_t n_ext,
+                                             uint32_t unit_shift, uint32_t tile_shift, StridedPiece out[2]) {
+    return strided_row_pieces(op, row, row, k, n_ext, unit_shift, tile_shift, out);
 }
 
 // The spans of tile t of an op (t < strided_tile_count(op)).

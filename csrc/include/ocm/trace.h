@@ -27,6 +27,9 @@ struct OpCounters {
     uint64_t n_acc = 0, n_acc_ops = 0, bytes_acc = 0;
     // strided converting ops (ocm_copy_onesided_quant_strided): calls, ops, 16-bit source bytes, record bytes
     uint64_t n_quant_strided = 0, n_quant_strided_ops = 0, bytes_quant_strided_src = 0, bytes_quant_strided_wire = 0;
+    // indexed ops (ocm_copy_onesided_indexed): calls, ops, rows named, nominal bytes (rows * row_bytes),
+    // rows skipped for an index outside its table (counted when their count is reported)
+    uint64_t n_indexed = 0, n_indexed_ops = 0, n_indexed_rows = 0, bytes_indexed = 0, n_indexed_skipped = 0;
 };
 
 bool trace_enabled();  // OCM_TRACE=0 disables the roctx ranges

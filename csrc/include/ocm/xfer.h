@@ -151,6 +151,12 @@ hipError_t xfer_batch_graph_node(hipGraph_t graph, hipGraphNode_t dep, const Xfe
 struct XferStridedArgs;
 hipError_t xfer_strided_launch(const XferStridedArgs &a, const XferTuning &t, hipStream_t stream);
 
+// Indexed lists (ocm/indexed.h: the descriptors, the bounds rule and the host plan): one
+// launch; a.grid from xfer_batch_grid, a.wave_op from list_wave_ops, a.skipped a device
+// word the kernel counts skipped rows into.
+struct XferIndexedArgs;
+hipError_t xfer_indexed_launch(const XferIndexedArgs &a, const XferTuning &t, hipStream_t stream);
+
 // Accumulate lists (ocm/acc.h: the element rule, the tile count and the descriptor
 // packing): one launch; a.grid from xfer_batch_grid, a.wave_op from list_wave_ops.
 // Stores are nontemporal (t.nontemporal), plain into a pool wholly in the pinned host tier.

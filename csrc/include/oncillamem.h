@@ -230,6 +230,59 @@ struct ocm_strided_params {
     uint32_t reserved;       /* must be 0 */
 };
 int ocm_copy_onesided_strided(ocm_alloc_t a, const struct ocm_strided_params *ops, int n_ops, int flags);
+/* Indexed one-sided copies (gather / scatter by row number): each side is a table of
+ * rows (offset, stride, number of rows), and which row of it row j of the op is comes
+ * from an index array. For j = 0 .. rows - 1, with lr = lidx[j] when the local side has
+ * an index and j when it has none, and rr likewise for the remote side, the op moves
+ * row_bytes bytes between local[local_offset + lr * local_stride] and
+ * remote[remote_offset + rr * remote_stride], in the direction of ocm_copy_onesided
+ * (op_flag 1 = put). Both index arrays, `rows` entries of index_type each, live in the
+ * LOCAL half (device memory on the kernel path) at local_index_offset and
+ * remote_index_offset; OCM_INDEX_NONE: that side has no index. They are read when the
+ * transfer runs, so they may be written on the GPU just before it (order the op after
+ * that work with ocm_stream_wait, as for any data of the local half). Ops of one call and
+ * rows of one op run concurrently, puts and gets mixed, as ONE gfx950 launch when the
+ * local half is device memory. No alignment is asked of offsets, strides or row_bytes.
+ *
+ * Out-of-range indices: row j is skipped, moving nothing on either side, when either of
+ * its indices is outside [0, table rows) of its side; indices are compared as unsigned, so
+ * negative ones are out of range. Skipped rows are counted once each. A blocking call
+ * that skipped k > 0 rows still moves every other row, then returns -1 and
+ * ocm_last_error() names k; after an OCM_BATCH_ASYNC call the next ocm_wait(a) returns -1
+ * once in the same way. Later ops on the allocation are unaffected.
+ *
+ * Duplicate destination rows (duplicates in the index of the side being written, or rows
+ * written by two ops of a call) have no defined result: which source wins is undefined
+ * and pieces of different sources may mix. Duplicates on the side being read are fine
+ * (an embedding lookup).
+ *
+ * Per op (checked at the call): index_type known and at least one index; rows,
+ * local_rows and remote_rows < 2^32; per side with more than one table row, stride >=
+ * row_bytes; per side, the table's last row ends inside its half; a side without an
+ * index has at least `rows` table rows; each index array is aligned to its element size
+ * and lies inside the local half; for a get, no index array overlaps the op's local
+ * table. An op with rows == 0 or row_bytes == 0 does nothing, whatever else it says.
+ * flags and ordering as for ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait,
+ * ocm_stream_wait/signal). Out of scope: transfer plans (ocm_plan_add takes ocm_params
+ * only), the copy service, converting and accumulate variants, index-times-stride
+ * (layer-major) ops and scatter-add. */
+#define OCM_INDEX_NONE (~0ull)
+enum ocm_index_type { OCM_INDEX_I32 = 1, OCM_INDEX_I64 = 2 };
+struct ocm_indexed_params {        /* 88 bytes */
+    uint64_t local_offset;         /* first byte of local table row 0 */
+    uint64_t remote_offset;        /* first byte of remote table row 0 */
+    uint64_t row_bytes;            /* any value; 0 = empty op */
+    uint64_t rows;                 /* rows moved = entries of each index array, < 2^32; 0 = empty op */
+    uint64_t local_stride;         /* bytes between local table rows */
+    uint64_t remote_stride;        /* bytes between remote table rows */
+    uint64_t local_index_offset;   /* byte offset IN THE LOCAL HALF of `rows` indices, or OCM_INDEX_NONE */
+    uint64_t remote_index_offset;  /* same, for the remote side */
+    uint64_t local_rows;           /* rows the local table has  (< 2^32) */
+    uint64_t remote_rows;          /* rows the remote table has (< 2^32) */
+    int32_t  op_flag;              /* 1 = put, 0 = get */
+    uint32_t index_type;           /* enum ocm_index_type, both arrays alike */
+};
+int ocm_copy_onesided_indexed(ocm_alloc_t a, const struct ocm_indexed_params *ops, int n_ops, int flags);
 /* One-sided accumulate (the counterpart of MPI_Accumulate): the remote half holds fp32
  * accumulators, the local half elements of `dtype`, and for every element i of every op
  *     remote_f32[i] = remote_f32[i] + scale * widen(local[i]).

@@ -8,6 +8,7 @@
 // quant.cpp    converting one-sided ops (ocm_copy_onesided_quant: MXFP8 records)
 // quant_strided.cpp  strided converting ops (ocm_copy_onesided_quant_strided: one MXFP8 record per row)
 // strided.cpp  strided one-sided ops (ocm_copy_onesided_strided: rows, one stride per side)
+// indexed.cpp  indexed one-sided ops (ocm_copy_onesided_indexed: rows picked by index arrays in the local half)
 // acc.cpp      one-sided accumulate (ocm_copy_onesided_accumulate: remote fp32 += scale * local)
 // libocm.cpp   the C ABI (oncillamem.h)
 // config.cpp   the environment's knobs, parsed once per ocm_init into State::cfg
@@ -114,6 +115,14 @@ struct lib_alloc {
     hipEvent_t dep_ev = nullptr;    // ocm_stream_wait: external work the next op depends on
     bool dep_pending = false;
     int plans = 0;                  // ocm_plan stages that reference this allocation
+    // Indexed ops (indexed.cpp): rows skipped for an index outside its table. The kernel
+    // counts them up in a device word that is never reset; after every launch the word is
+    // copied to a pinned host word on the same stream, and `skip_seen` is how much of it
+    // has been reported. `skip_host_path`: rows the host path skipped in async calls.
+    unsigned long long *skip_dev = nullptr;
+    unsigned long long *skip_host = nullptr;
+    uint64_t skip_seen = 0;
+    uint64_t skip_host_path = 0;
 };
 #pragma GCC diagnostic pop
 
@@ -489,6 +498,13 @@ int service_xfer(XferArgs x, unsigned solo_tiles, bool hbm, bool strict);
 void before_launch();
 
 // ---- descriptor lists (batches and their kin): lists.h
+
+// ---- indexed ops (indexed.cpp)
+// Rows that `a`'s completed async indexed ops skipped and no call has reported yet: 0 when
+// there are none, else -1 with the error set, once (ocm_wait).
+int indexed_take_skips(lib_alloc *a);
+// Frees the allocation's skip words (ocm_free).
+void indexed_release(lib_alloc *a);
 
 // ---- network tier (net.cpp)
 void net_drop(const std::string &ep);

@@ -40,6 +40,16 @@ void ocm_x_quant_strided_counters(uint64_t out[4]) {
     out[3] = c.bytes_quant_strided_wire;
 }
 
+// The indexed counters, likewise: calls, ops, rows named, nominal bytes, rows skipped.
+void ocm_x_indexed_counters(uint64_t out[5]) {
+    const OpCounters &c = S().ctr;
+    out[0] = c.n_indexed;
+    out[1] = c.n_indexed_ops;
+    out[2] = c.n_indexed_rows;
+    out[3] = c.bytes_indexed;
+    out[4] = c.n_indexed_skipped;
+}
+
 // Raw 64-byte handle of extent i (tests: the network tier's capability checks).
 int ocm_x_extent_handle(ocm_alloc_t a, int i, uint8_t *out) {
     if (!a || !out || i < 0 || (size_t)i >= a->ext.size()) return -1;

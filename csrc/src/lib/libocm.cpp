@@ -349,6 +349,7 @@ static int free_impl(ocm_alloc_t a) {
         a->batch_dev = a->batch_host = nullptr;
         a->batch_up = nullptr;
     }
+    indexed_release(a);
     if (a->ev) {
         DeviceGuard g(s.device);
         (void)hipEventDestroy(a->ev);
@@ -453,11 +454,14 @@ int ocm_wait(ocm_alloc_t a) {
     std::lock_guard<std::recursive_mutex> lk(s.mu);
     if (a) {
         if (!s.allocs.count(a)) OCM_FAIL(-1, "ocm_wait: unknown allocation");
-        return wait_alloc(a);
+        const int rc = wait_alloc(a);
+        return rc != 0 ? rc : indexed_take_skips(a);
     }
     int rc = 0;  // NULL: every allocation
     for (auto *x : s.allocs) rc |= wait_alloc(x);
-    return rc | sync_stream();
+    rc |= sync_stream();
+    for (auto *x : s.allocs) rc |= indexed_take_skips(x);
+    return rc;
 }
 
 static bool range_ok(uint64_t off, uint64_t n, uint64_t cap) { return off <= cap && n <= cap - off; }

@@ -1,6 +1,6 @@
 // What the kinds of descriptor list share on the host (batches in batch.cpp, converting
 // ops in quant.cpp, strided ops in strided.cpp, strided converting ops in
-// quant_strided.cpp, accumulates in acc.cpp): how a
+// quant_strided.cpp, indexed ops in indexed.cpp, accumulates in acc.cpp): how a
 // call is entered and accounted, how launch arguments are filled from the pair and the
 // plan (ocm/list.h), how a large list's descriptors and wave table are packed for the
 // device, and the upload, launch and completion of one list (run_list). A kind brings

@@ -1,0 +1,68 @@
+"""An embedding table in remote memory, looked up by id (oncilla_amd.models.RemoteEmbedding).
+
+    python examples/embedding_offload.py            # CPU-only daemons: the host path (works anywhere)
+    python examples/embedding_offload.py --gpu 0    # daemons and the app on MI355X #0: one kernel per lookup
+
+1. start a 3-daemon mesh; 2. load a random table into a remote half striped over the two
+peers; 3. look rows up by id, with repeats, each lookup ONE indexed get whose ids stay
+where they are (on the GPU with --gpu), and check them against torch.index_select;
+4. scatter new rows into the table and read them back; 5. an id outside the table is
+skipped, counted and reported.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from oncilla_amd import api  # noqa: E402
+from oncilla_amd.models import RemoteEmbedding  # noqa: E402
+from oncilla_amd.parallel import Mesh  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpu", type=int, default=None)
+    ap.add_argument("--rows", type=int, default=20000)
+    ap.add_argument("--dim", type=int, default=128)
+    args = ap.parse_args()
+    if args.gpu is None:
+        os.environ["OCM_NO_GPU"] = "1"
+    gpus = [args.gpu] * 3 if args.gpu is not None else None
+    kind = api.OCM_REMOTE_GPU if args.gpu is not None else api.OCM_REMOTE_RDMA
+    dev = f"cuda:{args.gpu}" if args.gpu is not None else "cpu"
+    g = torch.Generator().manual_seed(0)
+    with Mesh(3, gpus=gpus, policy="stripe") as mesh:
+        with api.Client(daemon_rank=0, gpu=args.gpu, ns=mesh.ns) as c:
+            emb = RemoteEmbedding(c, args.rows, args.dim, torch.float16, max_ids=2048, kind=kind, stripe_unit=1 << 16)
+            table = torch.randn((args.rows, args.dim), generator=g).to(torch.float16)
+            emb.load(table.to(dev))
+            for dtype in (torch.int64, torch.int32):
+                ids = torch.randint(0, args.rows, (2048,), generator=g).to(dtype)
+                ids[100:110] = ids[0]  # repeats are fine on the side being read
+                rows = emb.lookup(ids.to(dev))
+                emb.wait()
+                assert torch.equal(rows.cpu(), torch.index_select(table, 0, ids.long()))
+            # scatter: unique ids
+            ids = torch.randperm(args.rows, generator=g)[:512]
+            new = torch.randn((512, args.dim), generator=g).to(torch.float16)
+            emb.update(ids.to(dev), new.to(dev))
+            table[ids] = new
+            assert torch.equal(emb.lookup(ids.to(dev), async_=False).cpu(), new)
+            # an id outside the table moves nothing and is reported
+            bad = torch.tensor([3, args.rows, 5, -1])
+            try:
+                emb.lookup(bad.to(dev), async_=False)
+                raise SystemExit("an id outside the table went unreported")
+            except IndexError as e:
+                print("out of range:", e)
+            assert torch.equal(emb.out[[0, 2]].cpu(), table[[3, 5]])
+            print(f"{args.rows} x {args.dim} fp16 table in remote memory: lookups equal index_select;",
+                  {k: v for k, v in api.indexed_counters().items()})
+            emb.close()
+
+
+if __name__ == "__main__":
+    main()

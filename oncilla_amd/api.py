@@ -97,6 +97,28 @@ class OcmQuantStridedParams(ctypes.Structure):
     ]
 
 
+class OcmIndexedParams(ctypes.Structure):
+    """struct ocm_indexed_params (88 bytes)."""
+
+    _fields_ = [
+        ("local_offset", ctypes.c_uint64),
+        ("remote_offset", ctypes.c_uint64),
+        ("row_bytes", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("local_stride", ctypes.c_uint64),
+        ("remote_stride", ctypes.c_uint64),
+        ("local_index_offset", ctypes.c_uint64),
+        ("remote_index_offset", ctypes.c_uint64),
+        ("local_rows", ctypes.c_uint64),
+        ("remote_rows", ctypes.c_uint64),
+        ("op_flag", ctypes.c_int32),
+        ("index_type", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(OcmIndexedParams) == 88
+
+
 class OcmAccParams(ctypes.Structure):
     """struct ocm_acc_params (32 bytes)."""
 
@@ -220,6 +242,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_copy_onesided_quant": (i32, [vp, ctypes.POINTER(OcmQuantParams), i32, i32]),
             "ocm_copy_onesided_quant_strided": (i32, [vp, ctypes.POINTER(OcmQuantStridedParams), i32, i32]),
             "ocm_copy_onesided_strided": (i32, [vp, ctypes.POINTER(OcmStridedParams), i32, i32]),
+            "ocm_copy_onesided_indexed": (i32, [vp, ctypes.POINTER(OcmIndexedParams), i32, i32]),
             "ocm_copy_onesided_accumulate": (i32, [vp, ctypes.POINTER(OcmAccParams), i32, i32]),
             "ocm_stream_wait": (i32, [vp, vp]),
             "ocm_plan_create": (vp, []),
@@ -246,6 +269,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_x_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_acc_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_quant_strided_counters": (None, [ctypes.POINTER(u64)]),
+            "ocm_x_indexed_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_stats": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_health": (None, [ctypes.POINTER(u64)]),
             "ocm_x_tick_stats": (ctypes.c_int, [ctypes.POINTER(u64)]),
@@ -336,6 +360,10 @@ OCM_ACC_BF16 = 2
 OCM_ACC_FP16 = 3
 ACC_COUNTER_KEYS = ["n_acc", "n_acc_ops", "bytes_acc"]
 QUANT_STRIDED_COUNTER_KEYS = ["n_quant_strided", "n_quant_strided_ops", "bytes_quant_strided_src", "bytes_quant_strided_wire"]
+OCM_INDEX_NONE = (1 << 64) - 1  # an indexed op's side without an index array
+OCM_INDEX_I32 = 1
+OCM_INDEX_I64 = 2
+INDEXED_COUNTER_KEYS = ["n_indexed", "n_indexed_ops", "n_indexed_rows", "bytes_indexed", "n_indexed_skipped"]
 
 
 class Plan:
@@ -505,6 +533,52 @@ def quant_strided_ops(ops, dtype, format="mxfp8") -> BatchOps:
     b.keep = rec
     b.quant_strided = True
     return b
+
+
+def index_type_of(dtype) -> int:
+    """enum ocm_index_type of a torch or numpy integer dtype, of "int32" / "int64", or of the enum value itself."""
+    if isinstance(dtype, int):
+        return dtype
+    name = str(dtype).replace("torch.", "")
+    try:
+        return {"int32": OCM_INDEX_I32, "int": OCM_INDEX_I32, "int64": OCM_INDEX_I64, "long": OCM_INDEX_I64}[name]
+    except KeyError:
+        raise ValueError(f"index arrays hold int32 or int64, not {dtype}") from None
+
+
+def indexed_ops(ops, index_type=OCM_INDEX_I64) -> BatchOps:
+    """Descriptor list for Allocation.indexed_batch from an (n, 11) integer array (or rows)
+    [op_flag, local_offset, remote_offset, row_bytes, rows, local_stride, remote_stride,
+    local_index_offset, remote_index_offset, local_rows, remote_rows], built once (no per-op
+    Python objects). A side without an index has OCM_INDEX_NONE (or -1) as its index offset.
+    index_type: the element type of every index array (see :func:`index_type_of`)."""
+    import numpy as np
+
+    if isinstance(ops, np.ndarray) and ops.dtype.kind in "iu":
+        a = ops.astype(np.uint64).reshape(-1, 11)  # -1 wraps to OCM_INDEX_NONE
+    else:  # Python integers: OCM_INDEX_NONE fits no int64
+        flat = np.array(ops, dtype=object).reshape(-1)
+        a = np.array([int(v) & OCM_INDEX_NONE for v in flat], dtype=np.uint64).reshape(-1, 11)
+    n = int(a.shape[0])
+    rec = np.zeros(max(1, n), dtype=np.dtype([("lo", "<u8"), ("ro", "<u8"), ("rb", "<u8"), ("rows", "<u8"), ("ls", "<u8"),
+                                              ("rs", "<u8"), ("li", "<u8"), ("ri", "<u8"), ("lr", "<u8"), ("rr", "<u8"),
+                                              ("flag", "<i4"), ("it", "<u4")]))
+    if n:
+        for col, name in enumerate(("flag", "lo", "ro", "rb", "rows", "ls", "rs", "li", "ri", "lr", "rr")):
+            rec[name][:n] = a[:, col]
+        rec["it"][:n] = index_type_of(index_type)
+    b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmIndexedParams)), n)
+    b.keep = rec
+    b.indexed = True
+    return b
+
+
+def indexed_counters() -> dict:
+    """This process's indexed-op counters (ocm_x_indexed_counters): calls, ops, rows named, nominal
+    bytes (rows * row_bytes), and rows skipped for an index outside its table (as reported)."""
+    out = (ctypes.c_uint64 * len(INDEXED_COUNTER_KEYS))()
+    load().ocm_x_indexed_counters(out)
+    return dict(zip(INDEXED_COUNTER_KEYS, [int(v) for v in out]))
 
 
 def quant_strided_counters() -> dict:
@@ -1013,6 +1087,20 @@ class Allocation:
             raise TypeError("accumulate_batch takes an acc_ops list, not a batch_ops, quant_ops or strided_ops one")
         if self._c.lib.ocm_copy_onesided_accumulate(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_accumulate: " + last_error())
+
+    def indexed_batch(self, ops, index_type=OCM_INDEX_I64, async_: bool = False) -> None:
+        """Indexed one-sided ops in one launch (ocm_copy_onesided_indexed): row j of an op moves
+        row_bytes bytes between row lidx[j] of the local table and row ridx[j] of the remote one
+        (a side without an index: row j), the index arrays living in the local half. Rows with an
+        index outside its table are skipped and counted: a blocking call then raises OcmError naming
+        the count after moving every other row, an async one makes the next wait() raise it. Duplicate
+        destination rows have no defined result. ops: an (n, 11) integer array (or rows) as for
+        :func:`indexed_ops` with `index_type`, or a prepared indexed_ops list."""
+        arr = ops if isinstance(ops, BatchOps) else indexed_ops(ops, index_type)
+        if not getattr(arr, "indexed", False):
+            raise TypeError("indexed_batch takes an indexed_ops list, not a batch_ops, quant_ops, strided_ops or acc_ops one")
+        if self._c.lib.ocm_copy_onesided_indexed(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
+            raise OcmError("ocm_copy_onesided_indexed: " + last_error())
 
     def strided_batch(self, ops, async_: bool = False) -> None:
         """Strided one-sided ops in one launch (ocm_copy_onesided_strided): row r of an op moves

@@ -68,7 +68,7 @@ class PagedKVOffload:
 
     def __init__(self, client: api.Client, num_gpu_blocks: int, num_pool_blocks: int, block_shape: Sequence[int],
                  dtype=None, kind: int = api.OCM_REMOTE_GPU, flags: int = api.OCM_ALLOC_STRIPE, stripe_unit: int = 0,
-                 remote_rank: int = -1, compress=None, layers: int = 0):
+                 remote_rank: int = -1, compress=None, layers: int = 0, indexed_ids: int = 0):
         import torch
 
         self.dtype = dtype or torch.float16
@@ -105,11 +105,26 @@ class PagedKVOffload:
             self.pool_block_bytes = self.layers * self.pool_block_bytes
         lead = (self.layers, num_gpu_blocks) if self.layers else (num_gpu_blocks,)
         local_bytes = math.prod(lead) * self.block_bytes
+        # swap_out_indexed / swap_in_indexed: a tail of the local half for two arrays of
+        # `indexed_ids` int64 block ids (0: no tail, the half is the cache alone)
+        self.indexed_ids = int(indexed_ids)
+        if self.indexed_ids < 0:
+            raise ValueError("indexed_ids must be 0 or the most blocks one indexed swap names")
+        if self.indexed_ids and (self.layers or compress):
+            raise ValueError("indexed swaps cover the plain cache only: no layers (an index-times-stride op) "
+                             "and no compress")
+        self._ids_off = (local_bytes + 15) // 16 * 16
+        cache_bytes = local_bytes
+        if self.indexed_ids:
+            local_bytes = self._ids_off + 2 * 8 * self.indexed_ids
         self.alloc = client.alloc(kind, local_bytes=local_bytes,
                                   remote_bytes=num_pool_blocks * self.pool_block_bytes, remote_rank=remote_rank,
                                   flags=flags, stripe_unit=stripe_unit)
         # The cache the model reads and writes: a zero-copy view of the local half.
-        self.gpu_cache = self.alloc.local_tensor(self.dtype)[: local_bytes // elem].view(*lead, *self.block_shape)
+        self.gpu_cache = self.alloc.local_tensor(self.dtype)[: cache_bytes // elem].view(*lead, *self.block_shape)
+        if self.indexed_ids:
+            ids = self.alloc.local_tensor(torch.uint8)[self._ids_off: self._ids_off + 16 * self.indexed_ids]
+            self._ids = ids.view(torch.int64).view(2, self.indexed_ids)  # [0]: GPU block ids, [1]: pool block ids
 
     def _quant_ops(self, pairs, put: bool) -> api.BatchOps:
         # One op per block, never a coalesced run: a run's record would hold all its codes and
@@ -201,8 +216,57 @@ class PagedKVOffload:
             self.alloc.stream_signal()
         return ops.n
 
+    def _swap_indexed(self, gpu_ids, pool_ids, put: bool, async_: bool) -> int:
+        if self.layers or self.compress:
+            raise ValueError("indexed swaps cover the plain cache only: no layers (an index-times-stride op) "
+                             "and no compress")
+        if not self.indexed_ids:
+            raise ValueError("indexed swaps need the id region: construct with indexed_ids=N")
+        k = int(gpu_ids.numel())
+        if k != int(pool_ids.numel()):
+            raise ValueError("one pool block id per GPU block id")
+        if k > self.indexed_ids:
+            raise ValueError(f"{k} blocks in one indexed swap, the id region holds {self.indexed_ids}")
+        if k == 0:
+            return 0
+        # onto the id region on torch's current stream (no host sync, whichever device the ids are on)
+        self._ids[0, :k].copy_(gpu_ids.reshape(-1), non_blocking=True)
+        self._ids[1, :k].copy_(pool_ids.reshape(-1), non_blocking=True)
+        bb = self.block_bytes
+        op = [[1 if put else 0, 0, 0, bb, k, bb, bb, self._ids_off, self._ids_off + 8 * self.indexed_ids,
+               self.num_gpu_blocks, self.num_pool_blocks]]
+        self.alloc.stream_wait()  # after the copies above and the kernels that produced ids and blocks
+        try:
+            self.alloc.indexed_batch(api.indexed_ops(op, api.OCM_INDEX_I64), async_=async_)
+        except api.OcmError as e:
+            if "skipped" in str(e):
+                raise IndexError(f"indexed swap: {e}") from None
+            raise
+        if async_:
+            self.alloc.stream_signal()
+        return 1
+
+    def swap_out_indexed(self, gpu_ids, pool_ids, async_: bool = True) -> int:
+        """swap_out with the block ids in tensors (on the GPU: chosen by a scheduler kernel): GPU block
+        gpu_ids[i] goes to pool block pool_ids[i], as ONE indexed op with both index arrays and no host
+        loop over blocks. pool_ids must be unique (duplicate destinations have no defined result). An id
+        outside its cache skips that block; the call (blocking) or the next wait() (async) then raises
+        IndexError. Plain caches only: with `layers` or `compress` it raises ValueError. Returns the
+        number of ops issued."""
+        return self._swap_indexed(gpu_ids, pool_ids, True, async_)
+
+    def swap_in_indexed(self, pool_ids, gpu_ids, async_: bool = True) -> int:
+        """swap_in likewise: pool block pool_ids[i] comes into GPU block gpu_ids[i] (gpu_ids unique);
+        torch's current stream waits for the copies."""
+        return self._swap_indexed(gpu_ids, pool_ids, False, async_)
+
     def wait(self) -> None:
-        self.alloc.wait()
+        try:
+            self.alloc.wait()
+        except api.OcmError as e:
+            if "skipped" in str(e):
+                raise IndexError(f"indexed swap: {e}") from None
+            raise
 
     def close(self) -> None:
         self.alloc.free()
