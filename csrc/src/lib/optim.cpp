@@ -11,10 +11,13 @@
 // second pair instead (ocm/optim.h: AdamAccArgs), scaled, and can zero them in the same pass.
 // ocm_x_acc_sumsq reduces such accumulators to their sum of squares and non-finite count
 // (ocm/acc_norm.h), from which ocm_x_clip_scale makes that scale for a clipped step.
+// ocm_x_adam_rows is the row-sparse step of an embedding table that itself lives in a remote
+// half (ocm/adam_rows.h): ids on the GPU pick the rows, nothing else is read or written.
 #include <cmath>
 
 #include "internal.h"
 #include "ocm/acc_norm.h"
+#include "ocm/adam_rows.h"
 #include "ocm/optim.h"
 
 using namespace ocm;
@@ -186,9 +189,60 @@ int acc_norm_run(const char *who, ocm_alloc_t grads, int count, const uint64_t *
     return 0;
 }
 
+
+// The row-sparse step (ocm/adam_rows.h): the spaces of both pairs are prepared and every check
+// is made before the launch, so a refusal writes nothing.
+int adam_rows_run(const char *who, ocm_alloc_t table, ocm_alloc_t state, const ocm_adam_rows *d, const void *ids,
+                  const void *g, const float hp[9], float gscale, unsigned long long *skipped, void *stream) {
+    State &s = S();
+    if (!table || !state || !d || !hp || (d->rows && (!ids || !g))) OCM_FAIL(-1, "%s: null argument", who);
+    AdamRowsArgs x;
+    std::memset(&x, 0, sizeof(x));
+    AdamBad bad = adam_prepare(state, hp, d->bf16 != 0, &x.c);
+    if (bad == ADAM_OK) bad = adam_space(table, &x.table);  // the same checks, the same wording, for the table's pair
+    switch (bad) {
+    case ADAM_NO_GPU: OCM_FAIL(-1, "%s needs a GPU", who);
+    case ADAM_EXTENTS:
+    case ADAM_NO_PAIR: OCM_FAIL(-1, "%s needs a remote half this GPU can address", who);
+    case ADAM_STRIPE: OCM_FAIL(-1, "%s: stripe unit unusable", who);
+    case ADAM_OK: break;
+    }
+    char why[256];
+    if (adam_rows_check_hp(hp, gscale, why, sizeof(why)) != 0 ||
+        adam_rows_check(*d, table->remote_bytes, state->remote_bytes, table == state, why, sizeof(why)) != 0)
+        OCM_FAIL(-1, "%s: %s", who, why);
+    if (d->rows == 0) return 0;
+    x.d = *d;
+    x.ids = ids;
+    x.g = g;
+    x.skipped = skipped;
+    x.gscale = gscale;
+    std::lock_guard<std::recursive_mutex> lk(s.mu);
+    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
+    if (wait_alloc(table) != 0) return -1;  // queued async ops on either allocation come first
+    if (state != table && wait_alloc(state) != 0) return -1;
+    DeviceGuard dg(s.device);
+    before_launch();
+    const hipError_t e = adam_rows_launch(x, knobs, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// Row-sparse ("lazy") Adam on an embedding table in `table`'s remote half with exp_avg,
+// exp_avg_sq and (bf16 tables) fp32 master rows in `state`'s, which may be `table`: the d->rows
+// ids at `ids` (device memory) pick the rows, row j of the gradient `g` (device memory, the
+// table's dtype) is fl32(gscale * g) of row ids[j]. hp as for ocm_x_adam, with no weight decay of
+// either kind. Rows whose id is outside [0, d->table_rows) are left alone and counted up in
+// *skipped (a device word, or null). Duplicate ids have no defined result. Queued on `stream`
+// behind the async ops queued on both allocations; no host wait.
+int ocm_x_adam_rows(ocm_alloc_t table, ocm_alloc_t state, const struct ocm_adam_rows *d, const void *ids, const void *g,
+                    const float hp[9], float gscale, unsigned long long *skipped, void *stream) {
+    return adam_rows_run("ocm_x_adam_rows", table, state, d, ids, g, hp, gscale, skipped, stream);
+}
 
 // The global gradient norm's raw material, computed where the accumulators live: for tensor i
 // of n[i] fp32 words at byte offset g_off[i] of `grads`' remote half, sumsq[i] (fp64) and

@@ -8,6 +8,13 @@ peers; 3. look rows up by id, with repeats, each lookup ONE indexed get whose id
 where they are (on the GPU with --gpu), and check them against torch.index_select;
 4. scatter new rows into the table and read them back; 5. an id outside the table is
 skipped, counted and reported.
+
+    python examples/embedding_offload.py --gpu 0 --train
+
+trains a second, fp32 table where it lives (oncilla_amd.models.RemoteEmbeddingAdam): a few steps of
+a toy regression on looked-up rows, each step ONE fused row-sparse Adam launch, checked against a
+dense torch replay of the same rule on the CPU. The fused step is a GPU kernel: without --gpu the
+library refuses it ("needs a GPU") and --train reports that instead of training some other way.
 """
 import argparse
 import os
@@ -18,8 +25,54 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from oncilla_amd import api  # noqa: E402
-from oncilla_amd.models import RemoteEmbedding  # noqa: E402
+from oncilla_amd.models import RemoteEmbedding, RemoteEmbeddingAdam  # noqa: E402
 from oncilla_amd.parallel import Mesh  # noqa: E402
+
+
+def train(c, kind, dev, rows, dim, g, steps=5, batch=1024):
+    """Pull looked-up rows towards target rows: loss = 0.5 * |emb[ids] - target[ids]|^2 summed, so the
+    gradient of a looked-up row is the difference, and ids drawn twice add up."""
+    import math
+
+    emb = RemoteEmbedding(c, rows, dim, torch.float32, max_ids=batch, kind=kind, stripe_unit=1 << 16)
+    table = torch.randn((rows, dim), generator=g)
+    target = torch.randn((rows, dim), generator=g)
+    emb.load(table.to(dev))
+    lr, b1, b2, eps = 1e-2, 0.9, 0.999, 1e-8
+    opt = RemoteEmbeddingAdam(emb, lr=lr, betas=(b1, b2), eps=eps)
+    m, v = torch.zeros_like(table), torch.zeros_like(table)
+    touched = torch.zeros(rows, dtype=torch.bool)
+    for t in range(1, steps + 1):
+        ids = torch.randint(0, rows, (batch,), generator=g)
+        looked = emb.lookup(ids.to(dev))  # sees the step before: no sync in between
+        grad = looked - target[ids].to(dev)
+        try:
+            opt.step(ids.to(dev), grad)
+        except api.OcmError as e:
+            print(f"--train: the fused row-sparse step did not run: {e}")
+            opt.close()
+            emb.close()
+            return False
+        # the dense replay on the CPU: the same rule, the global step in the bias corrections
+        uniq, inv = torch.unique(ids, return_inverse=True)
+        gsum = torch.zeros(len(uniq), dim).index_add_(0, inv, table[ids] - target[ids])
+        m[uniq] = m[uniq] + (1 - b1) * (gsum - m[uniq])
+        v[uniq] = b2 * v[uniq] + (1 - b2) * gsum * gsum
+        denom = v[uniq].sqrt() * (1 / math.sqrt(1 - b2 ** t)) + eps
+        table[uniq] = table[uniq] - lr / (1 - b1 ** t) * (m[uniq] / denom)
+        touched[uniq] = True
+    for r in range(0, rows, batch):
+        ids = torch.arange(r, min(r + batch, rows))
+        got = emb.lookup(ids.to(dev), async_=False).cpu()
+        same = ~touched[ids]
+        assert torch.equal(got[same], table[ids][same]), "a row that was never picked changed"
+        assert torch.allclose(got, table[ids], rtol=1e-4, atol=1e-5), "the trained table left the replay"
+    assert opt.skipped() == 0
+    print(f"--train: {steps} fused row-sparse Adam steps on a {rows} x {dim} fp32 table in remote memory "
+          f"({int(touched.sum())} rows touched) equal the dense replay")
+    opt.close()
+    emb.close()
+    return True
 
 
 def main():
@@ -27,6 +80,7 @@ def main():
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--rows", type=int, default=20000)
     ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--train", action="store_true", help="also train a table in place with the fused row-sparse Adam")
     args = ap.parse_args()
     if args.gpu is None:
         os.environ["OCM_NO_GPU"] = "1"
@@ -62,6 +116,8 @@ def main():
             print(f"{args.rows} x {args.dim} fp16 table in remote memory: lookups equal index_select;",
                   {k: v for k, v in api.indexed_counters().items()})
             emb.close()
+            if args.train:
+                train(c, kind, dev, args.rows, args.dim, g)
 
 
 if __name__ == "__main__":

@@ -119,6 +119,26 @@ class OcmIndexedParams(ctypes.Structure):
 assert ctypes.sizeof(OcmIndexedParams) == 88
 
 
+class OcmAdamRows(ctypes.Structure):
+    """struct ocm_adam_rows (csrc/include/ocm/adam_rows.h): the descriptor of one row-sparse Adam step."""
+    _fields_ = [
+        ("rows", ctypes.c_uint64),
+        ("dim", ctypes.c_uint64),
+        ("table_rows", ctypes.c_uint64),
+        ("index_type", ctypes.c_uint32),
+        ("bf16", ctypes.c_uint32),
+        ("table_off", ctypes.c_uint64),
+        ("table_stride", ctypes.c_uint64),
+        ("m_off", ctypes.c_uint64),
+        ("m_stride", ctypes.c_uint64),
+        ("v_off", ctypes.c_uint64),
+        ("v_stride", ctypes.c_uint64),
+        ("w_off", ctypes.c_uint64),
+        ("w_stride", ctypes.c_uint64),
+        ("g_stride", ctypes.c_uint64),
+    ]
+
+
 class OcmAccParams(ctypes.Structure):
     """struct ocm_acc_params (32 bytes)."""
 
@@ -292,6 +312,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_x_adam_multi_acc": (i32, [vp, vp, i32, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                            ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                            ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_uint32, i32, vp]),
+            "ocm_x_adam_rows": (i32, [vp, vp, ctypes.POINTER(OcmAdamRows), vp, vp, ctypes.POINTER(ctypes.c_float),
+                                      ctypes.c_float, vp, vp]),
             "ocm_x_acc_sumsq": (i32, [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp, vp, u64, vp]),
             "ocm_x_acc_sumsq_work_bytes": (u64, [i32]),
             "ocm_x_clip_scale": (ctypes.c_double, [ctypes.c_double, ctypes.c_double, ctypes.c_double]),
@@ -1180,6 +1202,46 @@ class Allocation:
             float(gscale), OCM_ADAM_ACC_ZERO if zero else 0, 1 if bf16 else 0, self._stream_handle(stream))
         if rc != 0:
             raise OcmError("ocm_x_adam_multi_acc: " + last_error())
+
+    def adam_rows(self, state, ids, grad, table, exp_avg, exp_avg_sq, hp, table_rows: int, master=None,
+                  gscale: float = 1.0, skipped=None, stream=None) -> None:
+        """ocm_x_adam_rows: row-sparse ("lazy") fused Adam on an embedding table in this allocation's
+        remote half, with its moments in `state`'s remote half (an Allocation, possibly this one).
+        ids: k int32 / int64 ids on the GPU; grad: the (k, dim) gradient on the GPU, float32 for a
+        float32 table, bfloat16 for a bfloat16 one (rows contiguous, any row stride). table, exp_avg,
+        exp_avg_sq and, for bfloat16, master (fp32 master rows in `state`): (byte offset of row 0, row
+        stride in bytes) of tables of table_rows rows. Only the rows ids pick are read or written: the
+        gradient of row ids[j] is fl32(gscale * grad[j]), the element rule is adam()'s, and hp is
+        adam()'s tuple with the caller's global step in the bias corrections and no weight decay of
+        either kind. Ids outside [0, table_rows) move nothing and are counted up in skipped[0] (an
+        int64 tensor on the GPU, or None). Duplicate ids have no defined result. Queued on `stream`
+        (default: torch's current stream)."""
+        import torch
+
+        if grad.dim() != 2 or ids.dim() != 1 or ids.numel() != grad.shape[0]:
+            raise ValueError("adam_rows takes k ids and a (k, dim) gradient")
+        if grad.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"adam_rows: gradient dtype {grad.dtype} (float32 and bfloat16 tables are served)")
+        bf16 = grad.dtype == torch.bfloat16
+        if bf16 and master is None:
+            raise ValueError("a bfloat16 table needs master (fp32 master rows in the state)")
+        k, dim = int(grad.shape[0]), int(grad.shape[1])
+        if k and grad.stride(1) != 1:
+            raise ValueError("adam_rows: the gradient's rows must be contiguous")
+        w = master if bf16 else (0, 0)
+        d = OcmAdamRows(k, dim, int(table_rows), index_type_of(ids.dtype), 1 if bf16 else 0, int(table[0]), int(table[1]),
+                        int(exp_avg[0]), int(exp_avg[1]), int(exp_avg_sq[0]), int(exp_avg_sq[1]), int(w[0]), int(w[1]),
+                        int(grad.stride(0)) if k > 1 else dim)
+        if skipped is not None and (skipped.dtype != torch.int64 or skipped.numel() < 1):
+            raise TypeError("adam_rows: skipped is an int64 tensor")
+        if stream is None and self._c.device < 0:  # the hook's own refusal, before torch is asked for a stream
+            raise OcmError("ocm_x_adam_rows needs a GPU")
+        rc = self._c.lib.ocm_x_adam_rows(
+            self.handle, state.handle, ctypes.byref(d), ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(grad.data_ptr()),
+            (ctypes.c_float * 9)(*_adam_hp(hp)), float(gscale),
+            ctypes.c_void_p(skipped.data_ptr() if skipped is not None else None), self._stream_handle(stream))
+        if rc != 0:
+            raise OcmError("ocm_x_adam_rows: " + last_error())
 
     def acc_sumsq(self, g_offs, ns, stream=None):
         """ocm_x_acc_sumsq: one read-only pass over fp32 accumulators in this allocation's remote

@@ -14,6 +14,10 @@ the rows can be consumed there without a host sync.
 Ids outside [0, num_rows) move nothing: their output rows keep what they held, they are
 counted, and IndexError names the count, at once for a blocking lookup and at ``wait()``
 for an async one.
+
+RemoteEmbeddingAdam trains such a table where it lives: one fused row-sparse Adam launch per
+step (ocm_x_adam_rows) on the rows whose ids were in the batch, with the moments (and, for a
+bfloat16 table, fp32 master rows) in the remote half of a second pair.
 """
 from __future__ import annotations
 
@@ -33,6 +37,8 @@ class RemoteEmbedding:
         import torch
 
         self.dtype = dtype or torch.float16
+        self.client = client
+        self._place = dict(kind=kind, flags=flags, stripe_unit=stripe_unit, remote_rank=remote_rank)
         self.num_rows, self.dim, self.max_ids = int(num_rows), int(dim), int(max_ids)
         if self.num_rows < 1 or self.dim < 1 or self.max_ids < 1:
             raise ValueError("num_rows, dim and max_ids must be positive")
@@ -109,3 +115,128 @@ class RemoteEmbedding:
 
     def close(self) -> None:
         self.alloc.free()
+
+
+class RemoteEmbeddingAdam:
+    """Row-sparse ("lazy") Adam for a RemoteEmbedding of float32 or bfloat16.
+
+    The state is a pair of its own, placed as the table is: exp_avg and exp_avg_sq tables of
+    num_rows x dim fp32 in its remote half, zeroed, and for a bfloat16 table fp32 master rows,
+    initialised from the table. ``step`` updates the rows whose ids it is given, and nothing
+    else, in one launch: the element rule is the dense fused Adam's (Allocation.adam), with the
+    global step count in the bias corrections for every row, so a row's moments do not move
+    while it is not picked. This is not torch.optim.SparseAdam's arithmetic (which adds eps
+    before the bias correction). There is no weight decay: what it would mean for rows that are
+    not picked is a policy nobody has chosen. float16 tables are not served."""
+
+    def __init__(self, emb: RemoteEmbedding, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0):
+        import torch
+
+        if emb.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"RemoteEmbeddingAdam serves float32 and bfloat16 tables, not {emb.dtype} "
+                            "(RemoteEmbedding's default dtype is float16: pass dtype=torch.float32 or torch.bfloat16)")
+        if weight_decay != 0.0:
+            raise ValueError("RemoteEmbeddingAdam has no weight decay: it is not defined for rows that are not picked")
+        self.emb, self.lr, self.betas, self.eps = emb, float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.bf16 = emb.dtype == torch.bfloat16
+        self.t = 0
+        n, dim, k = emb.num_rows, emb.dim, emb.max_ids
+        self.row_bytes = 4 * dim  # of every state table (fp32)
+        table = (n * self.row_bytes + 15) // 16 * 16
+        names = ("m", "v", "w") if self.bf16 else ("m", "v")
+        self.off = {name: i * table for i, name in enumerate(names)}
+        self._ids_off = (k * self.row_bytes + 15) // 16 * 16
+        self.state = emb.client.alloc(local_bytes=self._ids_off + 8 * k, remote_bytes=len(names) * table, **emb._place)
+        raw = self.state.local_tensor(torch.uint8)
+        self._stage = raw[:k * self.row_bytes].view(torch.float32).view(k, dim)
+        self._ids = {torch.int64: raw[self._ids_off: self._ids_off + 8 * k].view(torch.int64),
+                     torch.int32: raw[self._ids_off: self._ids_off + 4 * k].view(torch.int32)}
+        dev = self._stage.device
+        self._skipped = torch.zeros(1, dtype=torch.int64, device=dev) if dev.type == "cuda" else None
+        for r in range(0, n, k):
+            c = min(k, n - r)
+            for name in names:
+                if name == "w":  # the master starts as the table's value
+                    emb.alloc.get(0, r * emb.row_bytes, c * emb.row_bytes)
+                    self._stage[:c].copy_(emb.out[:c])
+                else:
+                    self._stage[:c].zero_()
+                self.state.stream_wait()
+                self.state.put(0, self.off[name] + r * self.row_bytes, c * self.row_bytes)  # blocking
+
+    def _hp(self, t: int) -> tuple:
+        import math
+
+        b1, b2 = self.betas
+        return (b1, b2, self.eps, 0.0, self.lr / (1 - b1 ** t), 1 / math.sqrt(1 - b2 ** t))
+
+    def step(self, ids, grad_rows=None, scale: float = 1.0) -> None:
+        """One step on table rows ``ids`` (int32 / int64, any shape, on the table's GPU) with the
+        gradient rows ``grad_rows`` (ids.numel() x dim), or ``step(sparse_grad)`` with a sparse COO
+        gradient of the table's shape, as nn.Embedding(sparse=True) produces. Duplicate ids are
+        coalesced with torch on the device (torch.unique and index_add_ in fp32; a sparse gradient by
+        coalesce()), the sum is cast to the table's dtype, and ONE ocm_x_adam_rows launch is queued on
+        torch's current stream: the gradient of a row is fl32(scale * sum). torch.unique (and
+        coalesce) sync the host for the number of distinct ids; the launch itself does not. Ids outside
+        the table move nothing and are counted (``skipped``). A later lookup() sees the step."""
+        import torch
+
+        if grad_rows is None:
+            sp = ids.coalesce()
+            if tuple(sp.shape) != (self.emb.num_rows, self.emb.dim) or sp.sparse_dim() != 1:
+                raise ValueError(f"the sparse gradient must be {self.emb.num_rows} x {self.emb.dim} with one sparse dimension")
+            uniq, g = sp.indices()[0].contiguous(), sp.values().float()
+        else:
+            ids = ids.reshape(-1)
+            if ids.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"ids must be int32 or int64, not {ids.dtype}")
+            if tuple(grad_rows.shape) != (ids.numel(), self.emb.dim):
+                raise ValueError(f"grad_rows must be {ids.numel()} x {self.emb.dim}")
+            uniq, inv = torch.unique(ids, return_inverse=True)  # a host sync: the count
+            g = torch.zeros((uniq.numel(), self.emb.dim), dtype=torch.float32, device=grad_rows.device)
+            g.index_add_(0, inv, grad_rows.float())
+        if uniq.numel() == 0:
+            return
+        g = g.to(self.emb.dtype).contiguous()
+        self.t += 1
+        emb, rb = self.emb, self.row_bytes
+        emb.alloc.adam_rows(self.state, uniq, g, (0, emb.row_bytes), (self.off["m"], rb), (self.off["v"], rb),
+                            self._hp(self.t), emb.num_rows, master=(self.off["w"], rb) if self.bf16 else None,
+                            gscale=scale, skipped=self._skipped)
+
+    def skipped(self) -> int:
+        """Rows skipped so far because their id was outside the table. A host sync; resets nothing."""
+        return int(self._skipped.item()) if self._skipped is not None else 0
+
+    def _rows(self, name: str, ids):
+        k = int(ids.numel())
+        if ids.dtype not in self._ids:
+            raise TypeError(f"ids must be int32 or int64, not {ids.dtype}")
+        if k > self.emb.max_ids:
+            raise ValueError(f"{k} ids in one call, the id region holds {self.emb.max_ids}")
+        if k == 0:
+            return self._stage[:0].clone()
+        self._ids[ids.dtype][:k].copy_(ids.reshape(-1), non_blocking=True)
+        rb = self.row_bytes
+        op = [[0, 0, self.off[name], rb, k, rb, rb, api.OCM_INDEX_NONE, self._ids_off, self.emb.max_ids, self.emb.num_rows]]
+        self.state.stream_wait()  # after the id copy and the steps queued on torch's stream
+        try:
+            self.state.indexed_batch(api.indexed_ops(op, api.index_type_of(ids.dtype)))
+        except api.OcmError as e:
+            raise _index_error(e) from None
+        return self._stage[:k].clone()
+
+    def moments(self, ids):
+        """(exp_avg rows, exp_avg_sq rows) of ``ids`` (at most max_ids), read back with indexed gets:
+        for tests and checkpoints."""
+        return self._rows("m", ids), self._rows("v", ids)
+
+    def master(self, ids):
+        """The fp32 master rows of ``ids`` (bfloat16 tables only)."""
+        if not self.bf16:
+            raise TypeError("only a bfloat16 table has master rows")
+        return self._rows("w", ids)
+
+    def close(self) -> None:
+        self.state.free()
