@@ -25,12 +25,6 @@
 
 #include "ocm/optim.h"
 
-#if defined(__HIPCC__)
-#define OCM_ACC_NORM_HD __host__ __device__
-#else
-#define OCM_ACC_NORM_HD
-#endif
-
 namespace ocm {
 
 // What one workgroup leaves for the finishing kernel, and what that kernel adds up.
@@ -41,13 +35,9 @@ struct AccNormPartial {
 static_assert(sizeof(AccNormPartial) == 16, "one 16-byte store per workgroup");
 
 // One launch: up to kAdamMaxTensors tensors, blockIdx.y picks one (descriptors in the kernarg
-// segment, as AdamMultiArgs). The first three fields are a state space as AdamAccArgs has it.
+// segment, as AdamMultiArgs).
 struct AccNormArgs {
-    char *ext[kXferMaxExtents];      // extent bases of the accumulator space
-    uint32_t n_ext;
-    uint32_t unit_shift;             // log2(stripe unit) when n_ext > 1
-    uint32_t host_acc;               // 1: the accumulators are all in the pinned host tier
-    uint32_t host_span;              // (set by the launcher) bytes of the host extent the kernel may touch
+    StateSpace space;                // the accumulators
     uint32_t count;
     AccNormPartial *work;            // count * gridDim.x partials, tensor-major (device memory)
     uint64_t n[kAdamMaxTensors];     // words
@@ -69,7 +59,7 @@ struct AccNormFinishArgs {
 };
 
 // ---- the element rule ----
-OCM_ACC_NORM_HD inline bool acc_norm_nonfinite(uint32_t bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
+OCM_LIST_HD inline bool acc_norm_nonfinite(uint32_t bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
 
 // ---- one tensor, checked before any launch ----
 // acc_bytes: the allocation's remote half. n is bounded first and the range tested as
@@ -176,7 +166,5 @@ inline void acc_norm_totals(double *sumsq, uint64_t *nonfinite, uint32_t count) 
 // what a.work holds. Defined in csrc/src/kernels/acc_norm.hip.
 hipError_t acc_norm_launch(const AccNormArgs &a, AccNormFinishArgs f, uint64_t work_bytes, const AdamKnobs &knobs,
                            hipStream_t stream);
-// The CU count the launch shape is made for (256 when it cannot be asked).
-int acc_norm_cus();
 
 }  // namespace ocm

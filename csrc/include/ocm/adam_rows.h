@@ -184,15 +184,9 @@ inline int adam_rows_check_hp(const float hp[9], float gscale, char *why, size_t
 #endif
 
 // ---- launch (optim_rows.hip) ----
-struct AdamRowsSpace {               // the table's pair, as state_ptr() takes it
-    char *ext[kXferMaxExtents];
-    uint32_t n_ext;
-    uint32_t unit_shift;             // log2(stripe unit) when n_ext > 1
-};
-
 struct AdamRowsArgs {
     AdamArgs c;                      // the state's pair and the hyper-parameters (wd 0, not decoupled)
-    AdamRowsSpace table;
+    StateSpace table;                // the table's pair
     ocm_adam_rows d;
     const void *ids;                 // device: d.rows ids of d.index_type
     const void *g;                   // device: d.rows x d.dim gradient, fp32 (16-byte aligned) or bf16 (8-byte)

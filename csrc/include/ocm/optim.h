@@ -10,15 +10,12 @@
 #include <cstdint>
 #include <cstring>
 
-#include "ocm/xfer.h"
+#include "ocm/state_space.h"
 
 namespace ocm {
 
-// What every tensor of a launch shares.
-struct AdamArgs {
-    char *ext[kXferMaxExtents];      // extent bases of the striped state space
-    uint32_t n_ext;
-    uint32_t unit_shift;             // log2(stripe unit) when n_ext > 1
+// What every tensor of a launch shares: the element rule's constants, and where the state lives.
+struct AdamHyper {
     float b1, b2, eps, wd;           // betas, eps, L2 weight decay
     float omb1, omb2;                // 1 - b1, 1 - b2: computed in double by the caller, rounded once
     float step_size;                 // lr / (1 - b1^t)
@@ -26,8 +23,10 @@ struct AdamArgs {
     uint32_t bf16;                   // 1: p and g are bf16; fp32 master weights at w_off in the state
     uint32_t decoupled;              // 1: AdamW (p *= decay before the step; wd unused)
     float decay;                     // 1 - lr * weight_decay (AdamW)
-    uint32_t host_state;             // 1: the state is all in the pinned host tier (PCIe-bound launch shape)
-    uint32_t host_span;              // (set by the launcher) bytes of the host extent the kernel may touch
+};
+struct AdamArgs {
+    StateSpace state;                // exp_avg, exp_avg_sq and (bf16) the master weights
+    AdamHyper h;
 };
 
 // One to kAdamMaxTensors parameters in one launch: blockIdx.y picks the tensor
@@ -48,13 +47,9 @@ constexpr int kAdamMaxTensors = 32;
 // multiply rounded on its own. AdamTensor::g is not read.
 #define OCM_ADAM_ACC_ZERO 1u         // store +0.0f over every accumulator word that was read
 struct AdamAccArgs {
-    char *ext[kXferMaxExtents];      // extent bases of the accumulator space
-    uint32_t n_ext;
-    uint32_t unit_shift;             // log2(stripe unit) when n_ext > 1
+    StateSpace space;                // the accumulators
     float gscale;
     uint32_t flags;                  // OCM_ADAM_ACC_*
-    uint32_t host_acc;               // 1: the accumulators are all in the pinned host tier
-    uint32_t host_span;              // (set by the launcher) bytes of the host extent the kernel may touch
     uint64_t g_off[kAdamMaxTensors]; // byte offset of element 0's accumulator (16-byte aligned), per tensor
 };
 struct AdamMultiArgs {
@@ -181,5 +176,7 @@ inline const char *adam_acc_why(AdamAccBad b) {
 // pass zeroes when a.acc.flags has OCM_ADAM_ACC_ZERO; t[].g is not read.
 hipError_t adam_remote_launch(const AdamMultiArgs &a, const AdamKnobs &knobs, hipStream_t stream,
                               bool from_acc = false);
+// The CU count the launch shapes of the optimizer kernels are made for (256 when it cannot be asked).
+int optim_cus();
 
 }  // namespace ocm

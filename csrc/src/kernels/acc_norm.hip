@@ -28,7 +28,6 @@ constexpr int kThreads = kAdamThreads;
 constexpr int kV = 4;        // vectors in flight per lane
 constexpr int kWave = 64;
 constexpr int kWaves = kThreads / kWave;
-constexpr int kAuxNT = 2;    // nontemporal buffer load, as the kHost Adam's
 constexpr int kRuns = 8;     // lanes of the finishing kernel per tensor
 static_assert(kRuns * kAdamMaxTensors == kThreads, "one workgroup finishes one launch");
 
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void acc_norm_kernel(AccNormArgs a) {
     const uint64_t lanes = (uint64_t)gridDim.x * kThreads;
     const uint64_t tid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     __amdgpu_buffer_rsrc_t rs;
-    if constexpr (kHost) rs = __builtin_amdgcn_make_buffer_rsrc(a.ext[0], 0, (int)a.host_span, 0x00020000);
+    if constexpr (kHost) rs = host_rsrc(a.space);
     double s = 0.0;
     uint64_t bad = 0;
     for (uint64_t base = tid; base < nvec; base += lanes * kV) {
@@ -55,10 +54,9 @@ __global__ __launch_bounds__(kThreads) void acc_norm_kernel(AccNormArgs a) {
             const uint64_t i = base + (uint64_t)k * lanes;
             if (i < nvec) {
                 if constexpr (kHost)
-                    g[k] = __builtin_bit_cast(
-                        f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(uint32_t)(g_off + (i << 4)), 0, kAuxNT));
+                    g[k] = host_ld(rs, g_off + (i << 4));
                 else
-                    g[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(state_ptr(a, g_off + (i << 4))));
+                    g[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(state_ptr(a.space, g_off + (i << 4))));
             }
         }
 #pragma unroll
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void acc_norm_kernel(AccNormArgs a) {
         }
     }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
-        for (uint64_t i = nvec << 2; i < n; i++) take(*reinterpret_cast<const float *>(state_ptr(a, g_off + 4 * i)), s, bad);
+        for (uint64_t i = nvec << 2; i < n; i++) take(*reinterpret_cast<const float *>(state_ptr(a.space, g_off + 4 * i)), s, bad);
     // the wave: lane l takes lane l + off, off = 32 .. 1; lane 0 ends with the wave's sum
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) {
@@ -154,39 +152,24 @@ __global__ __launch_bounds__(kThreads) void acc_norm_finish_kernel(AccNormFinish
 
 }  // namespace
 
-int acc_norm_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    return cus;
-}
-
 hipError_t acc_norm_launch(const AccNormArgs &a, AccNormFinishArgs f, uint64_t work_bytes, const AdamKnobs &knobs,
                            hipStream_t stream) {
     if (a.count > (uint32_t)kAdamMaxTensors) return hipErrorInvalidValue;
     if (!f.sumsq || !f.nonfinite || (f.totals && (!f.all_sumsq || !f.all_nonfinite))) return hipErrorInvalidValue;
     AccNormShape s{0, false, 0};
     if (a.count) {
-        if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || (a.n_ext > 1 && a.unit_shift < 4))
-            return hipErrorInvalidValue;
+        if (!state_space_ok(a.space)) return hipErrorInvalidValue;
         for (uint32_t k = 0; k < a.count; k++)
             if (a.g_off[k] & 15u) return hipErrorInvalidValue;
-        s = acc_norm_launch_shape(a.n, a.g_off, a.count, a.host_acc != 0, a.n_ext, acc_norm_cus(), knobs);
+        s = acc_norm_launch_shape(a.n, a.g_off, a.count, a.space.host != 0, a.space.n_ext, optim_cus(), knobs);
         // every workgroup stores one partial: the workspace must hold them all
         if (s.gx && (!a.work || (uint64_t)s.gx * a.count * sizeof(AccNormPartial) > work_bytes))
             return hipErrorInvalidValue;
     }
     if (s.gx) {
-        const dim3 grid(s.gx, a.count);
-        if (s.host) {
-            AccNormArgs h = a;
-            h.host_span = (uint32_t)s.span;  // below 2^32, or the host variant would not run
-            hipLaunchKernelGGL(acc_norm_kernel<true>, grid, dim3(kThreads), 0, stream, h);
-        } else {
-            hipLaunchKernelGGL(acc_norm_kernel<false>, grid, dim3(kThreads), 0, stream, a);
-        }
-        const hipError_t e = hipGetLastError();
+        const auto kernel = s.host ? acc_norm_kernel<true> : acc_norm_kernel<false>;
+        const hipError_t e = state_launch(kernel, dim3(s.gx, a.count), stream, a, s.host,
+                                          [&](AccNormArgs &x) { x.space.host_span = (uint32_t)s.span; });
         if (e != hipSuccess) return e;
     }
     if (a.count == 0 && !f.totals) return hipSuccess;

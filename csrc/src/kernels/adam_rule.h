@@ -7,7 +7,7 @@
 
 namespace ocm {
 
-__device__ __forceinline__ float adam1(float &p, float g, float &m, float &v, const AdamArgs &a) {
+__device__ __forceinline__ float adam1(float &p, float g, float &m, float &v, const AdamHyper &a) {
     if (a.decoupled)
         p = p * a.decay;  // AdamW: p *= 1 - lr * weight_decay, gradient untouched
     else if (a.wd != 0.f)

@@ -25,43 +25,27 @@ namespace {
 
 constexpr int kThreads = kAdamThreads;
 
-// state_ptr (state_space.h): where byte x of a state space lies, AdamArgs (moments, master
-// weights) or AdamAccArgs (gradient accumulators), each with its own extent table and stripe shift.
+// state_ptr (state_space.h): where byte x of a state space lies, the moments' and master
+// weights' or the gradient accumulators', each with its own extent table and stripe shift.
 // adam1, acc_grad, bf16_to_f32, f32_to_bf16 (adam_rule.h): the element rule, shared with optim_rows.hip.
 
-// ---- state in the pinned host tier, one extent (kHost) ----
-// PCIe, not HBM, bounds this: the state streams in and out over one x16 Gen5
-// link at once. Buffer loads/stores on the extent (uniform base, 32-bit lane
-// offsets) so the stores can carry sc1 (write-through), which streams into host
-// memory faster than nontemporal or plain stores (profiles/pcie_stream_r03.json:
-// 57.0 vs 55.5 GB/s), and a grid of its own (adam_launch_shape): PCIe reads
-// want fewer streams than HBM.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kAuxNT = 2, kAuxSC1 = 16;
-
 // One launch for up to kAdamMaxTensors parameters (see AdamMultiArgs).
-// kHost: the state is one pinned host-tier extent whose offsets fit 32 bits:
-// buffer loads, write-through (sc1) stores into host memory (above). With kAcc the
-// accumulators are such an extent too, behind a buffer resource of their own.
+// kHost: the state is one pinned host-tier extent whose offsets fit 32 bits: host_ld / host_st
+// (state_space.h) on a grid of its own (adam_launch_shape), as PCIe reads want fewer streams than
+// HBM. With kAcc the accumulators are such an extent too, behind a buffer resource of their own.
 template <bool kBf16, bool kHost, int kV = 4, bool kAcc = false>
 __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
     const AdamTensor &T = a.t[blockIdx.y];  // uniform: scalar loads from the kernarg segment
-    const AdamArgs &c = a.c;
-    const AdamAccArgs &ga = a.acc;
-    const uint64_t g_off = kAcc ? ga.g_off[blockIdx.y] : 0;
-    const bool zero = kAcc && (ga.flags & OCM_ADAM_ACC_ZERO);
+    const StateSpace &c = a.c.state, &ga = a.acc.space;
+    const AdamHyper &h = a.c.h;
+    const uint64_t g_off = kAcc ? a.acc.g_off[blockIdx.y] : 0;
+    const bool zero = kAcc && (a.acc.flags & OCM_ADAM_ACC_ZERO);
     const uint64_t nvec = T.n >> 2;
     const uint64_t lanes = (uint64_t)gridDim.x * kThreads;
     const uint64_t tid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     __amdgpu_buffer_rsrc_t rs, grs;
-    if constexpr (kHost) rs = __builtin_amdgcn_make_buffer_rsrc(c.ext[0], 0, (int)c.host_span, 0x00020000);
-    if constexpr (kHost && kAcc) grs = __builtin_amdgcn_make_buffer_rsrc(ga.ext[0], 0, (int)ga.host_span, 0x00020000);
-    auto host_ld = [](__amdgpu_buffer_rsrc_t r, uint64_t off) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(uint32_t)off, 0, kAuxNT));
-    };
-    auto host_st = [](__amdgpu_buffer_rsrc_t r, uint64_t off, f32x4 x) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), r, (int)(uint32_t)off, 0, kAuxSC1);
-    };
+    if constexpr (kHost) rs = host_rsrc(c);
+    if constexpr (kHost && kAcc) grs = host_rsrc(ga);
     for (uint64_t base = tid; base < nvec; base += lanes * kV) {
         f32x4 w[kV], m[kV], v[kV], g[kV];
         f32x4 *wp[kV], *mp[kV], *vp[kV], *gp[kV];
@@ -108,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     float wj = w[k][j], mj = m[k][j], vj = v[k][j];
-                    adam1(wj, kAcc ? acc_grad(ga.gscale, g[k][j]) : g[k][j], mj, vj, c);
+                    adam1(wj, kAcc ? acc_grad(a.acc.gscale, g[k][j]) : g[k][j], mj, vj, h);
                     w[k][j] = wj;
                     m[k][j] = mj;
                     v[k][j] = vj;
@@ -150,14 +134,14 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamMultiArgs a) {
                 wj = static_cast<float *>(T.p)[i];
             if constexpr (kAcc) {
                 float *gq = reinterpret_cast<float *>(state_ptr(ga, g_off + 4 * i));
-                gj = acc_grad(ga.gscale, *gq);
+                gj = acc_grad(a.acc.gscale, *gq);
                 if (zero) *gq = 0.f;
             } else if constexpr (kBf16) {
                 gj = bf16_to_f32(static_cast<const unsigned short *>(T.g)[i]);
             } else {
                 gj = static_cast<const float *>(T.g)[i];
             }
-            adam1(wj, gj, mj, vj, c);
+            adam1(wj, gj, mj, vj, h);
             *mq = mj;
             *vq = vj;
             if constexpr (kBf16) {
@@ -182,41 +166,36 @@ auto adam_kernel_for(bool bf16, const AdamShape &s) -> void (*)(AdamMultiArgs) {
 
 }  // namespace
 
-hipError_t adam_remote_launch(const AdamMultiArgs &a, const AdamKnobs &knobs, hipStream_t stream, bool from_acc) {
-    if (a.count == 0) return hipSuccess;
-    if (a.count > (uint32_t)kAdamMaxTensors) return hipErrorInvalidValue;
-    if (a.c.n_ext < 1 || a.c.n_ext > (uint32_t)kXferMaxExtents) return hipErrorInvalidValue;
-    if (a.c.n_ext > 1 && a.c.unit_shift < 4) return hipErrorInvalidValue;
-    if (from_acc && (a.acc.n_ext < 1 || a.acc.n_ext > (uint32_t)kXferMaxExtents ||
-                     (a.acc.n_ext > 1 && a.acc.unit_shift < 4)))
-        return hipErrorInvalidValue;
-    for (uint32_t k = 0; k < a.count; k++) {
-        const AdamTensor &t = a.t[k];
-        const uintptr_t pal = a.c.bf16 ? 7u : 15u;
-        const uintptr_t g = from_acc ? (uintptr_t)a.acc.g_off[k] & 15u : (uintptr_t)t.g & pal;
-        if (((uintptr_t)t.p & pal) || g || ((t.m_off | t.v_off | (a.c.bf16 ? t.w_off : 0)) & 15u))
-            return hipErrorInvalidValue;
-    }
+int optim_cus() {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
         cus = 256;
-    const AdamAccShape as = adam_acc_launch_shape(a.t, from_acc ? a.acc.g_off : nullptr, a.count, a.c.bf16,
-                                                  a.c.host_state, a.c.n_ext, a.acc.host_acc, a.acc.n_ext, cus, knobs);
+    return cus;
+}
+
+hipError_t adam_remote_launch(const AdamMultiArgs &a, const AdamKnobs &knobs, hipStream_t stream, bool from_acc) {
+    const StateSpace &state = a.c.state, &accs = a.acc.space;
+    const bool bf16 = a.c.h.bf16 != 0;
+    if (a.count == 0) return hipSuccess;
+    if (a.count > (uint32_t)kAdamMaxTensors) return hipErrorInvalidValue;
+    if (!state_space_ok(state) || (from_acc && !state_space_ok(accs))) return hipErrorInvalidValue;
+    for (uint32_t k = 0; k < a.count; k++) {
+        const AdamTensor &t = a.t[k];
+        const uintptr_t pal = bf16 ? 7u : 15u;
+        const uintptr_t g = from_acc ? (uintptr_t)a.acc.g_off[k] & 15u : (uintptr_t)t.g & pal;
+        if (((uintptr_t)t.p & pal) || g || ((t.m_off | t.v_off | (bf16 ? t.w_off : 0)) & 15u))
+            return hipErrorInvalidValue;
+    }
+    const AdamAccShape as = adam_acc_launch_shape(a.t, from_acc ? a.acc.g_off : nullptr, a.count, bf16, state.host,
+                                                  state.n_ext, accs.host, accs.n_ext, optim_cus(), knobs);
     const AdamShape &s = as.s;
     if (s.gx == 0) return hipSuccess;
-    void (*kernel)(AdamMultiArgs) = from_acc ? adam_kernel_for<true>(a.c.bf16, s) : adam_kernel_for<false>(a.c.bf16, s);
-    const dim3 grid(s.gx, a.count);
-    if (s.host) {
-        AdamMultiArgs h = a;
-        h.c.host_span = (uint32_t)s.span;  // below 2^32, or the host variant would not run
-        h.acc.host_span = (uint32_t)as.acc_span;  // likewise (0 without accumulators)
-        hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, h);
-    } else {
-        hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, a);
-    }
-    return hipGetLastError();
+    void (*kernel)(AdamMultiArgs) = from_acc ? adam_kernel_for<true>(bf16, s) : adam_kernel_for<false>(bf16, s);
+    return state_launch(kernel, dim3(s.gx, a.count), stream, a, s.host, [&](AdamMultiArgs &x) {
+        x.c.state.host_span = (uint32_t)s.span;
+        x.acc.space.host_span = (uint32_t)as.acc_span;
+    });
 }
 
 }  // namespace ocm
-

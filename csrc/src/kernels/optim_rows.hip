@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kRowsThreads) void adam_rows_kernel(AdamRowsArgs a)
     if (t >= t1) return;
     const uint32_t lane = threadIdx.x & 63;
     const ocm_adam_rows &d = a.d;
-    const AdamArgs &c = a.c;
+    const StateSpace &c = a.c.state;
     uint64_t j, k;  // tile t is piece k of row j
     indexed_locate(a.tiles_per_row, t, &j, &k);
     j = uniform64(j);
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kRowsThreads) void adam_rows_kernel(AdamRowsArgs a)
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 float wi = wv[u][i], mi = m[u][i], vi = v[u][i];
-                adam1(wi, acc_grad(a.gscale, g[u][i]), mi, vi, c);
+                adam1(wi, acc_grad(a.gscale, g[u][i]), mi, vi, a.c.h);
                 wv[u][i] = wi;
                 m[u][i] = mi;
                 v[u][i] = vi;
@@ -140,16 +140,12 @@ __global__ __launch_bounds__(kRowsThreads) void adam_rows_kernel(AdamRowsArgs a)
     }
 }
 
-bool space_ok(uint32_t n_ext, uint32_t unit_shift) {
-    return n_ext >= 1 && n_ext <= (uint32_t)kXferMaxExtents && (n_ext == 1 || (unit_shift >= 4 && unit_shift < 64));
-}
-
 }  // namespace
 
 hipError_t adam_rows_launch(const AdamRowsArgs &a, const AdamKnobs &knobs, hipStream_t stream) {
     const ocm_adam_rows &d = a.d;
     if (d.rows == 0) return hipSuccess;
-    if (!space_ok(a.c.n_ext, a.c.unit_shift) || !space_ok(a.table.n_ext, a.table.unit_shift)) return hipErrorInvalidValue;
+    if (!state_space_ok(a.c.state) || !state_space_ok(a.table)) return hipErrorInvalidValue;
     if (!a.ids || !a.g || d.dim == 0 || d.dim % 4 || d.rows >= (1ull << 32) || d.table_rows >= (1ull << 32) ||
         (d.index_type != OCM_INDEX_I32 && d.index_type != OCM_INDEX_I64))
         return hipErrorInvalidValue;
@@ -158,11 +154,7 @@ hipError_t adam_rows_launch(const AdamRowsArgs &a, const AdamKnobs &knobs, hipSt
         ((d.table_off | d.table_stride) & tal) || ((d.m_off | d.m_stride | d.v_off | d.v_stride) & 15u) ||
         (d.bf16 && ((d.w_off | d.w_stride) & 15u)))
         return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    const AdamRowsShape s = adam_rows_launch_shape(d.rows, d.dim, cus, knobs);
+    const AdamRowsShape s = adam_rows_launch_shape(d.rows, d.dim, optim_cus(), knobs);
     if (s.grid == 0) return hipSuccess;
     AdamRowsArgs x = a;
     x.grid = s.grid;

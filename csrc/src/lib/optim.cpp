@@ -25,39 +25,64 @@ using namespace ocmlib;
 
 namespace {
 
-// Before any launch: check that a kernel on this GPU can address the pair's remote
-// half, and fill the fields every launch shares (the extent table and stripe shift,
-// the hyper-parameters, where the state lives). adam_run words the errors.
-enum AdamBad { ADAM_OK = 0, ADAM_NO_GPU, ADAM_NO_PAIR, ADAM_EXTENTS, ADAM_STRIPE };
-
-// One state space (the moments' pair or the accumulators'): Space is AdamArgs or AdamAccArgs.
-template <class Space>
-AdamBad adam_space(ocm_alloc_t a, Space *x) {
-    if (S().device < 0) return ADAM_NO_GPU;
-    if (!is_pair(a->kind) || a->ext.empty() || !a->all_dev_ok) return ADAM_NO_PAIR;
-    if (a->ext.size() > (size_t)kXferMaxExtents) return ADAM_EXTENTS;
-    std::memset(x, 0, sizeof(*x));
-    if (pair_side(a, 4, x) < 0) return ADAM_STRIPE;
-    return ADAM_OK;
+// The start of every hook, after its null checks (lists.h: list_enter): takes the library lock
+// into `lk` (held until the caller returns), refuses a handle that is not a live allocation
+// before anything of it is read, and fills the state space `xa` of `a` and, unless `b` is null
+// (`xb` is then left alone), `xb` of `b`, or says why a kernel here cannot address one (`single`:
+// in ocm_x_adam's own words).
+int optim_enter(std::unique_lock<std::recursive_mutex> &lk, const char *who, bool single, ocm_alloc_t a, StateSpace *xa,
+                ocm_alloc_t b = nullptr, StateSpace *xb = nullptr) {
+    State &s = S();
+    lk = std::unique_lock<std::recursive_mutex>(s.mu);
+    if (!s.allocs.count(a) || (b && !s.allocs.count(b))) OCM_FAIL(-1, "%s: unknown allocation", who);
+    if (s.device < 0) OCM_FAIL(-1, "%s needs a GPU", who);
+    const std::pair<ocm_alloc_t, StateSpace *> sides[2] = {{a, xa}, {b, xb}};
+    for (const auto &[h, x] : sides) {
+        if (!h) continue;
+        const bool many = h->ext.size() > (size_t)kXferMaxExtents;
+        if (!is_pair(h->kind) || h->ext.empty() || !h->all_dev_ok || (many && !single))
+            OCM_FAIL(-1, "%s needs a remote half this GPU can address%s", who,
+                     single ? " (HBM or host tier, not another node)" : "");
+        if (many) OCM_FAIL(-1, "%s: too many extents", who);
+        std::memset(x, 0, sizeof(*x));
+        if (pair_side(h, 4, x) < 0) {
+            if (single) OCM_FAIL(-1, "%s: stripe unit %llu unusable", who, (unsigned long long)h->stripe_unit);
+            OCM_FAIL(-1, "%s: stripe unit unusable", who);
+        }
+        x->host = (!h->any_gpu && !h->any_net) ? 1u : 0u;
+    }
+    return 0;
 }
 
-bool host_tier(ocm_alloc_t a) { return !a->any_gpu && !a->any_net; }
+AdamKnobs adam_knobs(const Config &c) { return AdamKnobs{c.adam_host, c.adam_host_grid, c.adam_host_vec, c.adam_grid}; }
 
-AdamBad adam_prepare(ocm_alloc_t a, const float hp[9], bool bf16, AdamArgs *x) {
-    if (const AdamBad bad = adam_space(a, x)) return bad;
-    x->b1 = hp[0];
-    x->b2 = hp[1];
-    x->eps = hp[2];
-    x->wd = hp[3];
-    x->step_size = hp[4];
-    x->inv_sqrt_bc2 = hp[5];
-    x->decoupled = std::isnan(hp[6]) ? 0u : 1u;  // NaN: L2 Adam; else AdamW's weight multiplier
-    x->decay = hp[6];
-    x->omb1 = hp[7];
-    x->omb2 = hp[8];
-    x->host_state = host_tier(a) ? 1u : 0u;
-    x->bf16 = bf16 ? 1u : 0u;
-    return ADAM_OK;
+// The end of every hook, under the lock, every check made: queued async ops on the allocations
+// come first, then `launch` (which may queue several kernels) on the library's GPU, with the knobs.
+template <class Launch>
+int optim_launch(const char *who, ocm_alloc_t a, ocm_alloc_t b, Launch launch) {
+    if (wait_alloc(a) != 0) return -1;
+    if (b && b != a && wait_alloc(b) != 0) return -1;
+    DeviceGuard dg(S().device);
+    before_launch();
+    const hipError_t e = launch(adam_knobs(S().cfg));
+    if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
+    return 0;
+}
+
+AdamHyper adam_hyper(const float hp[9], bool bf16) {
+    AdamHyper h{};
+    h.b1 = hp[0];
+    h.b2 = hp[1];
+    h.eps = hp[2];
+    h.wd = hp[3];
+    h.step_size = hp[4];
+    h.inv_sqrt_bc2 = hp[5];
+    h.decoupled = std::isnan(hp[6]) ? 0u : 1u;  // NaN: L2 Adam; else AdamW's weight multiplier
+    h.decay = hp[6];
+    h.omb1 = hp[7];
+    h.omb2 = hp[8];
+    h.bf16 = bf16 ? 1u : 0u;
+    return h;
 }
 
 // n fp32 state elements at byte offset `off` lie inside the remote half.
@@ -73,38 +98,23 @@ struct AdamAccSource {
     uint32_t flags;
 };
 
-// The one path behind the four entry points: `count` tensors, kAdamMaxTensors per launch.
-// `who` names the caller in the messages; the list entry points (`multi`) word some of them
-// their own way and name the tensor at fault. `acc`: the gradients are accumulators (`g` is
-// then unused). Every tensor is checked before the first launch: a bad one never leaves
-// some parameters a step ahead of the others.
+// The one path behind the four dense entry points: `count` tensors, kAdamMaxTensors per launch.
+// The list entry points (`multi`) name the tensor at fault. `acc`: the gradients are
+// accumulators (`g` is then unused). Every tensor is checked before the first launch: a bad
+// one never leaves some parameters a step ahead of the others.
 int adam_run(const char *who, bool multi, ocm_alloc_t a, int count, void *const *p, const void *const *g,
              const uint64_t *n, const uint64_t *w_off, const uint64_t *m_off, const uint64_t *v_off, const float hp[9],
              bool bf16, void *stream, const AdamAccSource *acc = nullptr) {
-    State &s = S();
     if (!a || count < 0 || (count && (!p || (!acc && !g) || !n || !m_off || !v_off || (bf16 && !w_off))) || !hp ||
         (!multi && (!p[0] || !g[0])) || (acc && (!acc->grads || (count && !acc->g_off))))
         OCM_FAIL(-1, "%s: null argument", who);
-    AdamMultiArgs x;
-    std::memset(&x, 0, sizeof(x));
-    const char *const which = multi ? "" : " (HBM or host tier, not another node)";
-    AdamBad bad = adam_prepare(a, hp, bf16, &x.c);
-    if (bad == ADAM_OK && acc) {  // the same checks, the same wording, for the gradient allocation
-        bad = adam_space(acc->grads, &x.acc);
+    AdamMultiArgs x{};
+    std::unique_lock<std::recursive_mutex> lk;
+    if (optim_enter(lk, who, !multi, a, &x.c.state, acc ? acc->grads : nullptr, &x.acc.space) != 0) return -1;
+    x.c.h = adam_hyper(hp, bf16);
+    if (acc) {
         x.acc.gscale = acc->gscale;
         x.acc.flags = acc->flags;
-        x.acc.host_acc = host_tier(acc->grads) ? 1u : 0u;
-    }
-    switch (bad) {
-    case ADAM_NO_GPU: OCM_FAIL(-1, "%s needs a GPU", who);
-    case ADAM_EXTENTS:
-        if (!multi) OCM_FAIL(-1, "%s: too many extents", who);
-        [[fallthrough]];
-    case ADAM_NO_PAIR: OCM_FAIL(-1, "%s needs a remote half this GPU can address%s", who, which);
-    case ADAM_STRIPE:
-        if (multi) OCM_FAIL(-1, "%s: stripe unit unusable", who);
-        OCM_FAIL(-1, "%s: stripe unit %llu unusable", who, (unsigned long long)a->stripe_unit);
-    case ADAM_OK: break;
     }
     for (int i = 0; i < count; i++) {
         if (!p[i] || (!acc && !g[i])) OCM_FAIL(-1, "%s: tensor %d has no data", who, i);
@@ -118,23 +128,19 @@ int adam_run(const char *who, bool multi, ocm_alloc_t a, int count, void *const 
                                               acc->grads == a);
         if (why != ADAM_ACC_OK) OCM_FAIL(-1, "%s: tensor %d: %s", who, i, adam_acc_why(why));
     }
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
-    if (wait_alloc(a) != 0) return -1;  // queued async ops on this allocation come first
-    if (acc && acc->grads != a && wait_alloc(acc->grads) != 0) return -1;  // the accumulates, for one
-    DeviceGuard dg(s.device);
-    before_launch();
-    for (int k0 = 0; k0 < count; k0 += kAdamMaxTensors) {
-        x.count = (uint32_t)std::min(count - k0, kAdamMaxTensors);
-        for (uint32_t j = 0; j < x.count; j++) {
-            const int i = k0 + (int)j;
-            x.t[j] = AdamTensor{p[i], acc ? nullptr : g[i], n[i], bf16 ? w_off[i] : 0, m_off[i], v_off[i]};
-            if (acc) x.acc.g_off[j] = acc->g_off[i];
+    return optim_launch(who, a, acc ? acc->grads : nullptr, [&](const AdamKnobs &knobs) {
+        hipError_t e = hipSuccess;
+        for (int k0 = 0; k0 < count && e == hipSuccess; k0 += kAdamMaxTensors) {
+            x.count = (uint32_t)std::min(count - k0, kAdamMaxTensors);
+            for (uint32_t j = 0; j < x.count; j++) {
+                const int i = k0 + (int)j;
+                x.t[j] = AdamTensor{p[i], acc ? nullptr : g[i], n[i], bf16 ? w_off[i] : 0, m_off[i], v_off[i]};
+                if (acc) x.acc.g_off[j] = acc->g_off[i];
+            }
+            e = adam_remote_launch(x, knobs, static_cast<hipStream_t>(stream), acc != nullptr);
         }
-        const hipError_t e = adam_remote_launch(x, knobs, static_cast<hipStream_t>(stream), acc != nullptr);
-        if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
-    }
-    return 0;
+        return e;
+    });
 }
 
 // The sum of squares and the non-finite count of `count` accumulator tensors of `grads`' remote
@@ -142,71 +148,56 @@ int adam_run(const char *who, bool multi, ocm_alloc_t a, int count, void *const 
 // finishing kernel. Every tensor is checked before the first launch: a refusal writes nothing.
 int acc_norm_run(const char *who, ocm_alloc_t grads, int count, const uint64_t *n, const uint64_t *g_off, double *sumsq,
                  uint64_t *nonfinite, void *work, uint64_t work_bytes, void *stream) {
-    State &s = S();
     if (!grads || (count > 0 && (!n || !g_off || !work)) || !sumsq || !nonfinite) OCM_FAIL(-1, "%s: null argument", who);
-    AccNormArgs x;
-    switch (adam_space(grads, &x)) {  // the Adam hooks' checks, the Adam hooks' wording
-    case ADAM_NO_GPU: OCM_FAIL(-1, "%s needs a GPU", who);
-    case ADAM_EXTENTS:
-    case ADAM_NO_PAIR: OCM_FAIL(-1, "%s needs a remote half this GPU can address", who);
-    case ADAM_STRIPE: OCM_FAIL(-1, "%s: stripe unit unusable", who);
-    case ADAM_OK: break;
-    }
-    x.host_acc = host_tier(grads) ? 1u : 0u;
+    AccNormArgs x{};
+    std::unique_lock<std::recursive_mutex> lk;
+    if (optim_enter(lk, who, false, grads, &x.space) != 0) return -1;
     int at = -1;
     if (const AccNormBad why = acc_norm_check_list(count, n, g_off, grads->remote_bytes, &at)) {
         if (at < 0) OCM_FAIL(-1, "%s: %s", who, acc_norm_why(why));
         OCM_FAIL(-1, "%s: tensor %d: %s", who, at, acc_norm_why(why));
     }
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
-    DeviceGuard dg(s.device);
-    const uint64_t need = acc_norm_work_bytes(count, acc_norm_cus(), knobs);
+    uint64_t need;
+    {
+        DeviceGuard dg(S().device);  // optim_cus asks the current device
+        need = acc_norm_work_bytes(count, optim_cus(), adam_knobs(S().cfg));
+    }
     if (work_bytes < need)
         OCM_FAIL(-1, "%s: workspace of %llu bytes is short of %llu", who, (unsigned long long)work_bytes,
                  (unsigned long long)need);
-    if (wait_alloc(grads) != 0) return -1;  // queued async ops on this allocation (the accumulates) come first
-    before_launch();
     x.work = static_cast<AccNormPartial *>(work);
-    int k0 = 0;
-    do {  // count == 0: the finishing kernel alone, for the zero totals
-        x.count = (uint32_t)std::min(count - k0, kAdamMaxTensors);
-        for (uint32_t j = 0; j < x.count; j++) {
-            x.n[j] = n[k0 + (int)j];
-            x.g_off[j] = g_off[k0 + (int)j];
-        }
-        AccNormFinishArgs f{};
-        f.sumsq = sumsq + k0;
-        f.nonfinite = nonfinite + k0;
-        k0 += (int)x.count;
-        f.totals = k0 >= count ? 1u : 0u;
-        f.total_count = (uint32_t)count;
-        f.all_sumsq = sumsq;
-        f.all_nonfinite = nonfinite;
-        const hipError_t e = acc_norm_launch(x, f, work_bytes, knobs, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
-    } while (k0 < count);
-    return 0;
+    return optim_launch(who, grads, nullptr, [&](const AdamKnobs &knobs) {
+        hipError_t e = hipSuccess;
+        int k0 = 0;
+        do {  // count == 0: the finishing kernel alone, for the zero totals
+            x.count = (uint32_t)std::min(count - k0, kAdamMaxTensors);
+            for (uint32_t j = 0; j < x.count; j++) {
+                x.n[j] = n[k0 + (int)j];
+                x.g_off[j] = g_off[k0 + (int)j];
+            }
+            AccNormFinishArgs f{};
+            f.sumsq = sumsq + k0;
+            f.nonfinite = nonfinite + k0;
+            k0 += (int)x.count;
+            f.totals = k0 >= count ? 1u : 0u;
+            f.total_count = (uint32_t)count;
+            f.all_sumsq = sumsq;
+            f.all_nonfinite = nonfinite;
+            e = acc_norm_launch(x, f, work_bytes, knobs, static_cast<hipStream_t>(stream));
+        } while (k0 < count && e == hipSuccess);
+        return e;
+    });
 }
-
 
 // The row-sparse step (ocm/adam_rows.h): the spaces of both pairs are prepared and every check
 // is made before the launch, so a refusal writes nothing.
 int adam_rows_run(const char *who, ocm_alloc_t table, ocm_alloc_t state, const ocm_adam_rows *d, const void *ids,
                   const void *g, const float hp[9], float gscale, unsigned long long *skipped, void *stream) {
-    State &s = S();
     if (!table || !state || !d || !hp || (d->rows && (!ids || !g))) OCM_FAIL(-1, "%s: null argument", who);
-    AdamRowsArgs x;
-    std::memset(&x, 0, sizeof(x));
-    AdamBad bad = adam_prepare(state, hp, d->bf16 != 0, &x.c);
-    if (bad == ADAM_OK) bad = adam_space(table, &x.table);  // the same checks, the same wording, for the table's pair
-    switch (bad) {
-    case ADAM_NO_GPU: OCM_FAIL(-1, "%s needs a GPU", who);
-    case ADAM_EXTENTS:
-    case ADAM_NO_PAIR: OCM_FAIL(-1, "%s needs a remote half this GPU can address", who);
-    case ADAM_STRIPE: OCM_FAIL(-1, "%s: stripe unit unusable", who);
-    case ADAM_OK: break;
-    }
+    AdamRowsArgs x{};
+    std::unique_lock<std::recursive_mutex> lk;
+    if (optim_enter(lk, who, false, state, &x.c.state, table, &x.table) != 0) return -1;
+    x.c.h = adam_hyper(hp, d->bf16 != 0);
     char why[256];
     if (adam_rows_check_hp(hp, gscale, why, sizeof(why)) != 0 ||
         adam_rows_check(*d, table->remote_bytes, state->remote_bytes, table == state, why, sizeof(why)) != 0)
@@ -217,15 +208,8 @@ int adam_rows_run(const char *who, ocm_alloc_t table, ocm_alloc_t state, const o
     x.g = g;
     x.skipped = skipped;
     x.gscale = gscale;
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
-    if (wait_alloc(table) != 0) return -1;  // queued async ops on either allocation come first
-    if (state != table && wait_alloc(state) != 0) return -1;
-    DeviceGuard dg(s.device);
-    before_launch();
-    const hipError_t e = adam_rows_launch(x, knobs, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) OCM_FAIL(-1, "%s launch: %s", who, hipGetErrorString(e));
-    return 0;
+    return optim_launch(who, table, state,
+                        [&](const AdamKnobs &knobs) { return adam_rows_launch(x, knobs, static_cast<hipStream_t>(stream)); });
 }
 
 }  // namespace
@@ -260,9 +244,8 @@ uint64_t ocm_x_acc_sumsq_work_bytes(int count) {
     State &s = S();
     if (s.device < 0 || count <= 0) return 0;
     std::lock_guard<std::recursive_mutex> lk(s.mu);
-    const AdamKnobs knobs{s.cfg.adam_host, s.cfg.adam_host_grid, s.cfg.adam_host_vec, s.cfg.adam_grid};
     DeviceGuard dg(s.device);
-    return acc_norm_work_bytes(count, acc_norm_cus(), knobs);
+    return acc_norm_work_bytes(count, optim_cus(), adam_knobs(s.cfg));
 }
 
 // ocm/acc_norm.h's clip_scale: the gscale of a step clipped to max_norm, in double.

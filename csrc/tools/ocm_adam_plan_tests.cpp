@@ -1,10 +1,15 @@
 // The fused Adam launch shape (ocm/optim.h: adam_launch_shape): grid, kernel variant,
-// host span and vectors per lane for lists of tensors, where the state lives and the knobs.
+// host span and vectors per lane for lists of tensors, where the state lives and the knobs;
+// and the state space the optimizer kernels share (ocm/state_space.h): the launch-time check
+// at its edges and the address arithmetic against its plain definition.
 // The expected values are written out here as numbers, worked out with the arithmetic the
 // launcher used before this function existed, not taken from the code under test.
 // Stand-alone: it sees the HIP headers through ocm/optim.h and links nothing of HIP, so
 // the build also makes an ASan + UBSan copy of it.
 #include <cstdio>
+#include <random>
+#include <set>
+#include <utility>
 #include <vector>
 
 #include "ocm/optim.h"
@@ -134,6 +139,58 @@ void test_knobs() {
     if (failures == before) std::printf("PASS knobs\n");
 }
 
+StateSpace space(uint32_t n_ext, uint32_t unit_shift) {
+    StateSpace s{};
+    s.n_ext = n_ext;
+    s.unit_shift = unit_shift;
+    return s;
+}
+
+void test_space() {
+    const int before = failures;
+    // state_space_ok: 1 .. kXferMaxExtents (8) extents; a striped space needs 4 <= shift < 64
+    for (const uint32_t shift : {0u, 3u, 4u, 63u, 64u}) {
+        CHECK(!state_space_ok(space(0, shift)), "no extents, shift %u: accepted", shift);
+        CHECK(state_space_ok(space(1, shift)), "one extent, shift %u: refused (not striped: the shift is unused)", shift);
+        CHECK(!state_space_ok(space(9, shift)), "9 extents, shift %u: accepted", shift);
+        const bool want = shift >= 4 && shift < 64;
+        CHECK(state_space_ok(space(2, shift)) == want, "2 extents, shift %u: expected %d", shift, (int)want);
+        CHECK(state_space_ok(space(8, shift)) == want, "8 extents, shift %u: expected %d", shift, (int)want);
+    }
+    // state_place against the definition: unit u = x >> shift lives on extent u % n at
+    // ((u / n) << shift) | (x & mask), in plain 64-bit arithmetic
+    std::mt19937_64 rng(20261020);
+    for (const uint32_t n : {1u, 2u, 3u, 5u, 6u, 7u, 8u})
+        for (const uint32_t shift : {4u, 12u, 21u}) {
+            const uint64_t unit = 1ull << shift;
+            std::vector<uint64_t> xs;
+            // around unit boundaries: the first byte, the last 16-byte vector of a unit, the first of the next;
+            // around unit 2^32, where the 32-bit arithmetic hands over to the 64-bit
+            const uint64_t n64 = n, k4g = 1ull << 32;
+            for (const uint64_t u : {n64 - 1, n64, n64 + 1, n64 + 2, 1000003 * n64, k4g - 2, k4g - 1, k4g, k4g + 1, k4g + n64})
+                for (const uint64_t in : {uint64_t{0}, unit - 16})
+                    xs.push_back((u << shift) + in);
+            // 16-byte aligned, below 2^60; every other one below unit 2^32, for the 32-bit arithmetic
+            for (int i = 0; i < 4096; i++) xs.push_back(((i & 1) ? rng() >> 4 : rng() >> (32 - shift)) & ~15ull);
+            std::set<std::pair<uint32_t, uint64_t>> seen;
+            std::set<uint64_t> distinct(xs.begin(), xs.end());
+            for (const uint64_t x : distinct) {
+                const uint64_t u = x >> shift;
+                const StatePlace p = state_place(n, shift, x);
+                CHECK(p.index == u % n && p.off == (((u / n) << shift) | (x & (unit - 1))),
+                      "n_ext %u shift %u x %llu: extent %u offset %llu", n, shift, (unsigned long long)x, p.index,
+                      (unsigned long long)p.off);
+                // a byte inside the vector stays with it
+                const StatePlace q = state_place(n, shift, x + 15);
+                CHECK(q.index == p.index && q.off == p.off + 15, "n_ext %u shift %u x %llu: the vector is split", n, shift,
+                      (unsigned long long)x);
+                CHECK(seen.insert({p.index, p.off}).second, "n_ext %u shift %u x %llu: a place taken twice", n, shift,
+                      (unsigned long long)x);
+            }
+        }
+    if (failures == before) std::printf("PASS space\n");
+}
+
 }  // namespace
 
 int main() {
@@ -141,6 +198,7 @@ int main() {
     test_lists();
     test_host_variant();
     test_knobs();
+    test_space();
     std::printf("%d failure(s)\n", failures);
     return failures ? 1 : 0;
 }

@@ -1,10 +1,15 @@
 """The fused-Adam oracle and bound (tests/adam_cases.py) checked on the CPU: the fp64 oracle
 against torch in float64, the fp32 replay of the kernel's rule inside the bound for every
 hyper-parameter set, six wrong rules outside it, and the bf16 rounding port on the crafted
-table. No GPU: what runs the kernels themselves is tests/test_gpu_adam.py."""
+table; and what every optimizer hook says to a handle that is no live allocation. No GPU: what
+runs the kernels themselves is tests/test_gpu_adam.py."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
+
+from oncilla_amd import api
 
 from adam_cases import (HP_SETS, MUTATIONS, QUANTITIES, STEPS, adam_oracle, adam_rule_fp32, bf16_table, bound, errors,
                         f32_to_bf16_np, hyper, kernel_hp, make_inputs, reference, torch_adam)
@@ -127,3 +132,36 @@ def test_bf16_rounding_port_on_the_crafted_table():
     bits = [int(x) & 0xFFFFFFFF for x in t]
     for src, dst in pairs.items():
         assert int(got[bits.index(src)]) == u(dst), hex(src)
+
+
+def test_optimizer_hooks_refuse_a_freed_handle(mesh_factory, monkeypatch):
+    """A handle that is not a live allocation is refused by name before anything of it is read,
+    as the list calls refuse it; a live one gets as far as the GPU check."""
+    monkeypatch.setenv("OCM_NO_GPU", "1")
+    m = mesh_factory(2)
+    with api.Client(daemon_rank=0, ns=m.ns) as c:
+        live = c.alloc(api.OCM_REMOTE_GPU, local_bytes=1 << 16, remote_bytes=1 << 16)
+        gone = c.alloc(api.OCM_REMOTE_GPU, local_bytes=1 << 16, remote_bytes=1 << 16)
+        stale = ctypes.c_void_p(gone.handle.value)
+        gone.free()
+        lib = api.load()
+        hp, rows = (ctypes.c_float * 9)(), api.OcmAdamRows()
+        buf = (ctypes.c_double * 8)()  # stands for every device pointer: no hook gets as far as reading one
+        ptr = ctypes.cast(buf, ctypes.c_void_p)
+        try:
+            for handle, said in ((stale, "unknown allocation"), (live.handle, "needs a GPU")):
+                calls = {
+                    "ocm_x_adam": lambda: lib.ocm_x_adam(handle, ptr, ptr, 8, 0, 64, hp, None),
+                    "ocm_x_acc_sumsq": lambda: lib.ocm_x_acc_sumsq(handle, 0, None, None, ptr, ptr, None, 0, None),
+                    "ocm_x_adam_rows": lambda: lib.ocm_x_adam_rows(handle, handle, ctypes.byref(rows), None, None, hp, 1.0,
+                                                                    None, None),
+                }
+                for name, call in calls.items():
+                    assert call() == -1, name
+                    assert api.last_error().endswith(said) and name in api.last_error(), (name, api.last_error())
+            # either of two handles: the live one does not vouch for the stale one
+            for table, state in ((live.handle, stale), (stale, live.handle)):
+                assert lib.ocm_x_adam_rows(table, state, ctypes.byref(rows), None, None, hp, 1.0, None, None) == -1
+                assert api.last_error().endswith("unknown allocation"), api.last_error()
+        finally:
+            live.free()

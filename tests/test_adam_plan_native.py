@@ -1,6 +1,8 @@
 """The fused Adam launch shape (csrc/include/ocm/optim.h, adam_launch_shape): which kernel
 variant runs and on what grid, for one tensor and for lists, on HBM and host-tier state and
-under every knob, against numbers from the launcher's arithmetic before the function existed.
+under every knob, against numbers from the launcher's arithmetic before the function existed;
+and the state space of the optimizer kernels (csrc/include/ocm/state_space.h): its launch-time
+check at every edge and its address arithmetic, both branches, against the plain definition.
 The stand-alone program csrc/tools/ocm_adam_plan_tests.cpp, as built and as built with
 ASan + UBSan (host code only, run directly: nothing is preloaded and nothing is loaded into
 Python)."""
@@ -8,7 +10,7 @@ import pytest
 
 from oncilla_amd.utils.paths import BUILD_DIR
 
-PARTS = ("one_tensor", "lists", "host_variant", "knobs")
+PARTS = ("one_tensor", "lists", "host_variant", "knobs", "space")
 
 
 @pytest.mark.parametrize("binary", ["ocm_adam_plan_tests", "ocm_adam_plan_tests_asan"])
