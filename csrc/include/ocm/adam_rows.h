@@ -62,7 +62,7 @@ OCM_STRIDED_HD inline bool adam_rows_picks(uint64_t id, uint64_t table_rows) { r
 
 // The launch: `grid` workgroups of kListWaves waves; wave w walks the tiles
 // list_wave_range(w, grid, total_tiles) gives it, tile t being piece k of row j by
-// indexed_locate(tiles_per_row, t). A pure function of k, dim, the CU count and the knobs:
+// list_locate(tiles_per_row, t). A pure function of k, dim, the CU count and the knobs:
 // enough waves that each has kAdamRowsInFlight tiles to keep in flight, at most
 // kAdamRowsWgPerCu workgroups a CU (k.grid > 0: that many workgroups, whatever the rule says).
 struct AdamRowsShape {

@@ -65,18 +65,6 @@ OCM_STRIDED_HD inline bool indexed_in_range(uint64_t index, uint64_t table_rows)
 
 OCM_STRIDED_HD inline uint64_t indexed_tile_count(const XferIndexedOp &op) { return (uint64_t)op.rows * op.tiles_per_row; }
 
-// Row j (of the op's `rows`) and piece k of tile t, relative to the op's first tile, for an op of
-// tiles_per_row tiles a row.
-OCM_STRIDED_HD inline void indexed_locate(uint64_t tiles_per_row, uint64_t t, uint64_t *j, uint64_t *k) {
-    if (tiles_per_row == 1) {  // rows of at most one tile (embedding rows, KV blocks): no divide
-        *j = t;
-        *k = 0;
-        return;
-    }
-    *j = t / tiles_per_row;
-    *k = t - *j * tiles_per_row;
-}
-
 #if !defined(__HIP_DEVICE_COMPILE__)
 // Index j of the array at byte `off` of the local half `base` (host memory), widened.
 inline uint64_t indexed_load_host(const char *base, uint64_t off, uint32_t index_type, uint64_t j) {
@@ -195,23 +183,11 @@ inline XferIndexedOp indexed_op(const struct ocm_indexed_params &p) {
 // ---- launch (xfer_indexed.hip) ----
 constexpr int kIndexedInlineOps = 16;  // ops carried in the kernarg segment
 
-struct XferIndexedArgs {
-    char *lin;
-    char *ext[8];                         // kXferMaxExtents
-    uint32_t unit_shift;
-    uint32_t n_ext;
-    uint32_t tile_shift;
-    uint32_t n_ops;
-    uint64_t total_tiles;
-    uint32_t grid;                        // workgroups (4 waves each)
-    uint32_t host_tier;                   // 1: every extent is pinned host memory (plain stores for puts)
-    const XferIndexedOp *ops;             // device copy when n_ops > kIndexedInlineOps
-    const uint32_t *wave_op;              // device: first op of each wave (n_ops > kIndexedInlineOps)
+struct XferIndexedArgs : ListArgs<XferIndexedOp, kIndexedInlineOps> {
     unsigned long long *skipped;          // device word: rows skipped, counted up (never reset by a launch)
     unsigned long long *skipped_host;     // pinned host word the launcher copies it to after the kernel (the kernel reads neither)
-    XferIndexedOp inline_ops[kIndexedInlineOps];
 };
-static_assert(sizeof(XferIndexedArgs) < 4096, "kernarg segment limit");
+static_assert(list_args_fit<XferIndexedArgs>, "kernarg segment limit");
 
 // Host-side plan: fills tiles_per_row and first_tile, returns total tiles.
 inline uint64_t xfer_indexed_plan(XferIndexedOp *ops, uint32_t n, uint32_t tile_shift) {

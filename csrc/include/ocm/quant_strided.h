@@ -16,6 +16,7 @@
 // (quant_strided.cpp) and the stand-alone test program (ocm_quant_strided_tests.cpp)
 // share; it needs no HIP.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
@@ -59,18 +60,6 @@ OCM_QS_HD inline uint32_t quant_strided_tiles_per_row(uint64_t row_elems) { retu
 // Tiles of an op (0 for an empty one): rows < 2^32 times tiles_per_row < 2^20.
 OCM_QS_HD inline uint64_t quant_strided_tile_count(const XferQuantStridedOp &op) {
     return (uint64_t)op.rows * op.tiles_per_row;
-}
-
-// Row and piece of tile t (relative to the op's first tile). The divide is by a
-// wave-uniform value; the kernel does it once per op a wave enters and then counts.
-OCM_QS_HD inline void quant_strided_locate(const XferQuantStridedOp &op, uint64_t t, uint64_t *row, uint32_t *k) {
-    if (op.tiles_per_row == 1) {  // rows of at most one tile (KV blocks): no divide
-        *row = t;
-        *k = 0;
-        return;
-    }
-    *row = t / op.tiles_per_row;
-    *k = (uint32_t)(t - *row * op.tiles_per_row);
 }
 
 // Piece k of row `row`: exactly the tile (k) of the plain converting op
@@ -163,20 +152,14 @@ inline XferQuantStridedOp quant_strided_op(const struct ocm_quant_strided_params
 // ---- launch (xfer_quant_strided.hip) ----
 constexpr int kQuantStridedInlineOps = 24;  // ops carried in the kernarg segment
 
-struct XferQuantStridedArgs {
-    char *lin;
-    char *ext[8];                         // kXferMaxExtents
-    uint32_t unit_shift;
-    uint32_t n_ext;
-    uint32_t tile_shift;                  // kQuantTileShift (tiles are cut in elements)
-    uint32_t n_ops;
-    uint64_t total_tiles;
-    uint32_t grid;                        // workgroups (4 waves each)
-    uint32_t host_tier;                   // 1: every extent is pinned host memory (plain stores for puts)
-    const XferQuantStridedOp *ops;        // device copy when n_ops > kQuantStridedInlineOps
-    const uint32_t *wave_op;              // device: first op of each wave (n_ops > kQuantStridedInlineOps)
-    XferQuantStridedOp inline_ops[kQuantStridedInlineOps];
-};
+// tile_shift is kQuantTileShift (tiles are cut in elements)
+struct XferQuantStridedArgs : ListArgs<XferQuantStridedOp, kQuantStridedInlineOps> {};
+static_assert(list_args_fit<XferQuantStridedArgs>, "kernarg segment limit");
+// the head and nothing else, where it has always been
+static_assert(offsetof(XferQuantStridedArgs, ops) == 104 && offsetof(XferQuantStridedArgs, wave_op) == 112 &&
+                  offsetof(XferQuantStridedArgs, inline_ops) == 120 &&
+                  sizeof(XferQuantStridedArgs) == 120 + kQuantStridedInlineOps * sizeof(XferQuantStridedOp),
+              "strided converting launch argument layout");
 
 // Host-side plan: fills tiles_per_row and first_tile, returns total tiles.
 inline uint64_t xfer_quant_strided_plan(XferQuantStridedOp *ops, uint32_t n, uint32_t /*tile_shift*/) {

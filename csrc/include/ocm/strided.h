@@ -18,6 +18,7 @@
 // (strided.cpp) and the stand-alone test program (ocm_strided_tests.cpp) share; it
 // needs no HIP.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
@@ -58,18 +59,6 @@ OCM_STRIDED_HD inline uint64_t strided_tiles_per_row(uint64_t row_bytes, uint32_
 // Tiles of an op (0 for an empty one). rows < 2^32 and rows * row_bytes fits the
 // remote half, so the product cannot overflow.
 OCM_STRIDED_HD inline uint64_t strided_tile_count(const XferStridedOp &op) { return (uint64_t)op.rows * op.tiles_per_row; }
-
-// Row and piece of tile t (relative to the op's first tile). The divide is by a
-// wave-uniform value; the kernel does it once per op a wave enters and then counts.
-OCM_STRIDED_HD inline void strided_locate(const XferStridedOp &op, uint64_t t, uint64_t *row, uint64_t *k) {
-    if (op.tiles_per_row == 1) {  // rows of at most one tile (KV blocks): no divide
-        *row = t;
-        *k = 0;
-        return;
-    }
-    *row = t / op.tiles_per_row;
-    *k = t - *row * op.tiles_per_row;
-}
 
 // The spans of piece k of a row of row_bytes whose first byte is lin_row_off of the linear
 // buffer and rem_row_off of the striped address space: 1, or 2 when the piece crosses a
@@ -120,7 +109,7 @@ OCM_STRIDED_HD inline int strided_row_pieces(const XferStridedOp &op, uint64_t r
 OCM_STRIDED_HD inline int strided_tile_pieces(const XferStridedOp &op, uint64_t t, uint32_t n_ext, uint32_t unit_shift,
                                               uint32_t tile_shift, StridedPiece out[2]) {
     uint64_t row, k;
-    strided_locate(op, t, &row, &k);
+    list_locate(op.tiles_per_row, t, &row, &k);
     return strided_row_pieces(op, row, k, n_ext, unit_shift, tile_shift, out);
 }
 
@@ -167,20 +156,12 @@ inline int strided_check_op(const struct ocm_strided_params &p, uint64_t local_b
 // ---- launch (xfer_strided.hip) ----
 constexpr int kStridedInlineOps = 24;  // ops carried in the kernarg segment
 
-struct XferStridedArgs {
-    char *lin;
-    char *ext[8];                         // kXferMaxExtents
-    uint32_t unit_shift;
-    uint32_t n_ext;
-    uint32_t tile_shift;
-    uint32_t n_ops;
-    uint64_t total_tiles;
-    uint32_t grid;                        // workgroups (4 waves each)
-    uint32_t host_tier;                   // 1: every extent is pinned host memory (plain stores for puts)
-    const XferStridedOp *ops;             // device copy when n_ops > kStridedInlineOps
-    const uint32_t *wave_op;              // device: first op of each wave (n_ops > kStridedInlineOps)
-    XferStridedOp inline_ops[kStridedInlineOps];
-};
+struct XferStridedArgs : ListArgs<XferStridedOp, kStridedInlineOps> {};
+static_assert(list_args_fit<XferStridedArgs>, "kernarg segment limit");
+// the head and nothing else, where it has always been
+static_assert(offsetof(XferStridedArgs, ops) == 104 && offsetof(XferStridedArgs, wave_op) == 112 &&
+                  offsetof(XferStridedArgs, inline_ops) == 120 && sizeof(XferStridedArgs) == 120 + kStridedInlineOps * sizeof(XferStridedOp),
+              "strided launch argument layout");
 
 // Host-side plan: fills tiles_per_row and first_tile, returns total tiles.
 inline uint64_t xfer_strided_plan(XferStridedOp *ops, uint32_t n, uint32_t tile_shift) {

@@ -19,8 +19,6 @@
 
 namespace ocm {
 
-constexpr int kXferMaxExtents = 8;
-
 struct XferArgs {
     char *lin;                       // linear side, already offset to the first byte
     char *ext[kXferMaxExtents];      // extent bases of the striped side
@@ -111,22 +109,10 @@ static_assert(sizeof(XferBatchOp) == 40, "batch op layout");
 
 constexpr int kXferInlineOps = 48;  // ops carried in the kernarg segment
 
-struct XferBatchArgs {
-    char *lin;
-    char *ext[kXferMaxExtents];
-    uint32_t unit_shift;
-    uint32_t n_ext;
-    uint32_t tile_shift;
-    uint32_t n_ops;
-    uint64_t total_tiles;
-    uint32_t grid;                        // workgroups (4 waves each)
-    uint32_t abs_lin;                     // 1: op.lin_off is an absolute device address (lin unused)
-    uint32_t host_tier;                   // 1: every extent is pinned host memory (PCIe launch shape)
-    uint32_t pad0;
-    const XferBatchOp *ops;               // device copy when n_ops > kXferInlineOps
-    const uint32_t *wave_op;              // device: first op of each wave (n_ops > kXferInlineOps)
-    XferBatchOp inline_ops[kXferInlineOps];
+struct XferBatchArgs : ListArgs<XferBatchOp, kXferInlineOps> {
+    uint32_t abs_lin;  // 1: op.lin_off is an absolute device address (lin unused)
 };
+static_assert(list_args_fit<XferBatchArgs>, "kernarg segment limit");
 
 // Host-side plan. Fills first_tile, returns total tiles (an empty op has none).
 inline uint64_t xfer_batch_plan(XferBatchOp *ops, uint32_t n, uint32_t tile_shift) {

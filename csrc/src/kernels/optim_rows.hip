@@ -3,7 +3,7 @@
 // live, with the dense kernel's element rule (adam_rule.h).
 //
 // A wave walks a contiguous tile range (list_wave_range), as xfer_indexed_kernel does; tile
-// t is piece k of row j (indexed_locate: one divide per wave, none for rows of one tile),
+// t is piece k of row j (list_locate: one divide per wave, none for rows of one tile),
 // 64 lanes x one 16-byte fp32 vector. For a tile of row j the wave loads ids[j] into a scalar
 // register (uniform32 / uniform64) and applies the bounds rule; a row whose id is outside
 // the table is skipped whole, and the wave that owns its piece 0 counts it, one device-scope
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kRowsThreads) void adam_rows_kernel(AdamRowsArgs a)
     const ocm_adam_rows &d = a.d;
     const StateSpace &c = a.c.state;
     uint64_t j, k;  // tile t is piece k of row j
-    indexed_locate(a.tiles_per_row, t, &j, &k);
+    list_locate(a.tiles_per_row, t, &j, &k);
     j = uniform64(j);
     k = uniform64(k);
     for (; t < t1; t += kV) {

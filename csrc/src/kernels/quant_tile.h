@@ -238,6 +238,37 @@ __device__ __forceinline__ void get_tile_mx4(const A &a, char *lin, uint64_t cod
     for (int k = 0; k < 4; k++) store16<true>(d + k, mx4_unpack8<BF16>(c[k], scale));
 }
 
+// One tile of either format, direction and element type: `dtype` is the op's
+// enum ocm_quant_dtype | enum ocm_quant_format word, `put` its direction, both wave-uniform.
+template <bool PUT_NT, class A>
+__device__ __forceinline__ void quant_tile(const A &a, char *lin, uint64_t codes, uint64_t scales, uint32_t ne,
+                                           uint32_t dtype, uint32_t put, uint32_t lane, uint8_t *sw) {
+    const bool bf16 = (dtype & kQuantElemMask) == kMx8Bf16;
+    if (quant_code_shift(dtype)) {
+        if (put) {
+            if (bf16)
+                put_tile_mx4<true, PUT_NT>(a, lin, codes, scales, ne, lane, sw);
+            else
+                put_tile_mx4<false, PUT_NT>(a, lin, codes, scales, ne, lane, sw);
+        } else {
+            if (bf16)
+                get_tile_mx4<true>(a, lin, codes, scales, ne, lane);
+            else
+                get_tile_mx4<false>(a, lin, codes, scales, ne, lane);
+        }
+    } else if (put) {
+        if (bf16)
+            put_tile<true, PUT_NT>(a, lin, codes, scales, ne, lane, sw);
+        else
+            put_tile<false, PUT_NT>(a, lin, codes, scales, ne, lane, sw);
+    } else {
+        if (bf16)
+            get_tile<true>(a, lin, codes, scales, ne, lane);
+        else
+            get_tile<false>(a, lin, codes, scales, ne, lane);
+    }
+}
+
 }  // namespace
 
 }  // namespace ocm

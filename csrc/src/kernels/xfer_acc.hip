@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void xfer_acc_kernel(XferBatchArgs a) {
 
 hipError_t xfer_acc_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (!kernels::list_args_valid<true, true>(a, kXferInlineOps)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<true>(a) || a.abs_lin) return hipErrorInvalidValue;  // lin_off is an offset here
     const bool nt = t.nontemporal && !a.host_tier;
     hipLaunchKernelGGL(nt ? xfer_acc_kernel<true> : xfer_acc_kernel<false>, dim3(a.grid), dim3(kThreads), 0, stream, a);
     return hipGetLastError();

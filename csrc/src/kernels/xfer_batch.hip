@@ -12,13 +12,7 @@ namespace ocm {
 
 namespace {
 
-constexpr uint32_t kBatchTileShift = 12;  // 4 KiB per wave-tile: 64 lanes x 16 B x 4 in flight
-constexpr int kBatchUnroll = 4;
-
-// One wave copies a span (n <= one wave-tile in the common case; any n works)
-// through pointers, with plain or nontemporal (NT) stores.
-template <bool NT>
-using WaveCopy = CopyCfg<64, kBatchUnroll, PointerAccess<NT>>;
+constexpr uint32_t kBatchTileShift = 12;  // 4 KiB per wave-tile: one round of WaveCopy (xfer_copy.h)
 
 // HOST: the host-tier shape. Its puts were meant to store write-through (sc1) into
 // the pinned host extents, as the PCIe streaming kernel does (57.0 vs 55.5 GB/s),
@@ -78,7 +72,7 @@ uint32_t xfer_batch_grid(uint64_t total_tiles, bool host_tier) {
 
 hipError_t xfer_batch_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (!kernels::list_args_valid<false, false>(a, kXferInlineOps)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<false>(a)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(batch_kernel_for(a, t), dim3(a.grid), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
@@ -87,7 +81,7 @@ hipError_t xfer_batch_graph_node(hipGraph_t graph, hipGraphNode_t dep, const Xfe
                                  hipGraphNode_t *node) {
     const size_t ndep = dep ? 1 : 0;
     if (a.total_tiles == 0 || a.n_ops == 0) return hipGraphAddEmptyNode(node, graph, dep ? &dep : nullptr, ndep);
-    if (!kernels::list_args_valid<false, false>(a, kXferInlineOps)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<false>(a)) return hipErrorInvalidValue;
     // Parameters by address: `a` must outlive the graph (the plan's stage
     // storage), whether or not the runtime copies them into the node.
     void *params[] = {const_cast<XferBatchArgs *>(&a)};

@@ -292,11 +292,41 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
 // capacity, else in device memory. Returns the op to start the walk from. (The early
 // return stays in the kernel: folded in here, the merge after it kept one instantiation
 // from reading the arguments in place, and it copied all 2 KiB of them to scratch.)
-template <class Args, class Op>
-__device__ __forceinline__ uint32_t list_wave_start(const Args &a, uint32_t w, const Op **ops) {
-    const bool inl = a.n_ops <= (uint32_t)(sizeof(Args::inline_ops) / sizeof(Op));
+template <class Args>
+__device__ __forceinline__ uint32_t list_wave_start(const Args &a, uint32_t w, const typename Args::Op **ops) {
+    static_assert(list_args_fit<Args>, "kernarg segment limit");
+    const bool inl = a.n_ops <= (uint32_t)Args::kInline;
     *ops = inl ? a.inline_ops : a.ops;
     return inl ? 0u : a.wave_op[w];
+}
+
+// What a wave of the row kernels hands list_enter_op (ocm/list.h) to read a descriptor's
+// first_tile with: into scalar registers.
+struct ListLoadUniform {
+    __device__ __forceinline__ uint64_t operator()(uint64_t v) const { return uniform64(v); }
+};
+
+// ---- the wave-granular copy of the batch, strided and indexed kernels ----
+constexpr int kWaveUnroll = 4;  // 64 lanes x 16 B x 4 in flight: one 4 KiB wave-tile a round
+
+template <bool NT>
+using WaveCopy = CopyCfg<64, kWaveUnroll, PointerAccess<NT>>;
+
+// One span (StridedPiece of ocm/strided.h), inside one stripe unit, of a list with launch
+// arguments `a`. HOST: every extent is pinned host memory; puts store plain there, as the
+// batch kernel's do.
+template <bool NT, bool HOST, class Args, class Piece>
+__device__ __forceinline__ void copy_piece(const Args &a, const Piece &p, uint32_t put) {
+    char *lp = a.lin + p.lin_off;
+    char *rp = stripe_ptr(a, a.n_ext, a.unit_shift, p.rem_off);
+    if (put) {
+        if (HOST)
+            copy_span<WaveCopy<false>>(rp, lp, p.n);
+        else
+            copy_span<WaveCopy<NT>>(rp, lp, p.n);
+    } else {
+        copy_span<WaveCopy<NT>>(lp, rp, p.n);
+    }
 }
 
 // Drain every wave's stores into L2, join the workgroup, then ONE system-scope

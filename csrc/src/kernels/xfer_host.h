@@ -26,18 +26,22 @@ __attribute__((visibility("hidden"))) inline int num_cus() {
     return cus;
 }
 
-// Whether a descriptor list with something to do can be launched (batch, converting,
-// strided and accumulate lists alike): `inline_cap` ops travel in the kernel arguments,
-// a longer list needs its device copy and wave table. UNIT16: the kernel maps 16-byte
-// vectors through the extents one by one, so a vector must fit a stripe unit.
-// NO_ABS_LIN: the kernel reads op.lin_off as an offset only.
-template <bool UNIT16, bool NO_ABS_LIN, class Args>
-inline bool list_args_valid(const Args &a, int inline_cap) {
+// Whether a descriptor list with something to do can be launched (every kind alike):
+// INLINE ops travel in the kernel arguments, a longer list needs its device copy and
+// wave table. UNIT16: the kernel maps 16-byte vectors through the extents one by one,
+// so a vector must fit a stripe unit.
+template <bool UNIT16, class Op, int INLINE>
+inline bool list_args_valid(const ListArgs<Op, INLINE> &a) {
     if (a.n_ext < 1 || a.n_ext > (uint32_t)kXferMaxExtents || a.grid == 0) return false;
     if (UNIT16 && a.n_ext > 1 && a.unit_shift < 4) return false;
-    if constexpr (NO_ABS_LIN)
-        if (a.abs_lin) return false;
-    return a.n_ops <= (uint32_t)inline_cap || (a.ops && a.wave_op);
+    return a.n_ops <= (uint32_t)INLINE || (a.ops && a.wave_op);
+}
+
+// Whether the tiles of a list of rows are cut so that a tile is at most one stripe unit
+// (two spans a tile at the most).
+template <class Op, int INLINE>
+inline bool list_tile_fits_unit(const ListArgs<Op, INLINE> &a) {
+    return a.tile_shift <= 63 && (a.n_ext <= 1 || a.tile_shift <= a.unit_shift);
 }
 
 }  // namespace ocm::kernels

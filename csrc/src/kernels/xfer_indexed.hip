@@ -4,8 +4,8 @@
 // geometry both kernels share.
 //
 // A wave walks a contiguous tile range, as in xfer_strided_kernel. Entering an op it
-// finds the row and piece of its first tile (indexed_locate: the only divide, skipped
-// for rows of one tile) and counts from then on. A wave owns whole tiles, so the two
+// finds the row and piece of its first tile (list_locate of ocm/list.h: the only divide,
+// skipped for rows of one tile) and counts from then on. A wave owns whole tiles, so the two
 // indices of a tile's row are one value per wave: they are loaded into scalar registers
 // (uniform32 / uniform64) when the wave enters a row, kept while the pieces of that row
 // go by, and loaded again when the row number increments. A row with an index outside
@@ -26,30 +26,7 @@
 
 namespace ocm {
 
-static_assert(sizeof(XferIndexedArgs::ext) == sizeof(XferBatchArgs::ext), "extent table of a pair");
-
 namespace {
-
-constexpr int kIndexedUnroll = 4;  // 64 lanes x 16 B x 4 in flight: one 4 KiB wave-tile a round
-
-template <bool NT>
-using WaveCopy = CopyCfg<64, kIndexedUnroll, PointerAccess<NT>>;
-
-// One span, inside one stripe unit. HOST: every extent is pinned host memory; puts
-// store plain there, as the batch and strided kernels' do.
-template <bool NT, bool HOST>
-__device__ __forceinline__ void copy_piece(const XferIndexedArgs &a, const StridedPiece &p, uint32_t put) {
-    char *lp = a.lin + p.lin_off;
-    char *rp = stripe_ptr(a, a.n_ext, a.unit_shift, p.rem_off);
-    if (put) {
-        if (HOST)
-            copy_span<WaveCopy<false>>(rp, lp, p.n);
-        else
-            copy_span<WaveCopy<NT>>(rp, lp, p.n);
-    } else {
-        copy_span<WaveCopy<NT>>(lp, rp, p.n);
-    }
-}
 
 // What a wave keeps of its op across the copy loops, in scalar registers (uniform32 /
 // uniform64, xfer_copy.h). The fields that only entering a row needs (enter_row) are
@@ -97,15 +74,11 @@ __global__ __launch_bounds__(kThreads) void xfer_indexed_kernel(XferIndexedArgs 
     bool ok = false;              // both indices of row j are inside their tables
     for (; t < t1; t++) {
         if (t >= next) {  // the wave's first tile, or the op's tiles are done: enter the op of tile t
-            for (;;) {
-                next = i + 1 < a.n_ops ? uniform64(ops[i + 1].first_tile) : ~0ull;
-                if (next > t) break;
-                i++;
-            }
+            next = list_enter_op(ops, a.n_ops, t, &i, ListLoadUniform());
             op.row_bytes = uniform64(ops[i].row_bytes);
             op.tiles_per_row = uniform64(ops[i].tiles_per_row);
             op.put = uniform32(ops[i].put);
-            indexed_locate(op.tiles_per_row, t - uniform64(ops[i].first_tile), &j, &k);
+            list_locate(op.tiles_per_row, t - uniform64(ops[i].first_tile), &j, &k);
             j = uniform64(j);
             k = uniform64(k);
             enter = true;
@@ -122,11 +95,7 @@ __global__ __launch_bounds__(kThreads) void xfer_indexed_kernel(XferIndexedArgs 
             copy_piece<NT, HOST>(a, p[0], op.put);
             if (np == 2) copy_piece<NT, HOST>(a, p[1], op.put);
         }
-        if (++k == op.tiles_per_row) {
-            k = 0;
-            j++;
-            enter = true;
-        }
+        if (list_next_piece(op.tiles_per_row, &j, &k)) enter = true;
     }
 }
 
@@ -134,9 +103,8 @@ __global__ __launch_bounds__(kThreads) void xfer_indexed_kernel(XferIndexedArgs 
 
 hipError_t xfer_indexed_launch(const XferIndexedArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (!kernels::list_args_valid<false, false>(a, kIndexedInlineOps) || !a.lin || !a.skipped) return hipErrorInvalidValue;
-    // a tile is at most one stripe unit (two spans a tile at the most)
-    if (a.tile_shift > 63 || (a.n_ext > 1 && a.tile_shift > a.unit_shift)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<false>(a) || !kernels::list_tile_fits_unit(a) || !a.lin || !a.skipped)
+        return hipErrorInvalidValue;
     auto kernel = a.host_tier    ? xfer_indexed_kernel<true, true>
                   : t.nontemporal ? xfer_indexed_kernel<true, false>
                                   : xfer_indexed_kernel<false, false>;

@@ -47,30 +47,7 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_kernel(XferBatchArgs a) {
         char *lin = a.lin + op.lin_off + 2ull * e0;
         const uint32_t cs = quant_code_shift(op.pad);  // elements per code byte, log2
         const uint64_t codes = op.rem_off + (e0 >> cs), scales = op.rem_off + (op.len >> cs) + (e0 >> 5);
-        const bool bf16 = (op.pad & kQuantElemMask) == kMx8Bf16;
-        if (cs) {
-            if (op.put) {
-                if (bf16)
-                    put_tile_mx4<true, PUT_NT>(a, lin, codes, scales, ne, lane, scale_lds[wl]);
-                else
-                    put_tile_mx4<false, PUT_NT>(a, lin, codes, scales, ne, lane, scale_lds[wl]);
-            } else {
-                if (bf16)
-                    get_tile_mx4<true>(a, lin, codes, scales, ne, lane);
-                else
-                    get_tile_mx4<false>(a, lin, codes, scales, ne, lane);
-            }
-        } else if (op.put) {
-            if (bf16)
-                put_tile<true, PUT_NT>(a, lin, codes, scales, ne, lane, scale_lds[wl]);
-            else
-                put_tile<false, PUT_NT>(a, lin, codes, scales, ne, lane, scale_lds[wl]);
-        } else {
-            if (bf16)
-                get_tile<true>(a, lin, codes, scales, ne, lane);
-            else
-                get_tile<false>(a, lin, codes, scales, ne, lane);
-        }
+        quant_tile<PUT_NT>(a, lin, codes, scales, ne, op.pad, op.put, lane, scale_lds[wl]);
     }
 }
 
@@ -78,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_kernel(XferBatchArgs a) {
 
 hipError_t xfer_quant_launch(const XferBatchArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (!kernels::list_args_valid<true, true>(a, kXferInlineOps)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<true>(a) || a.abs_lin) return hipErrorInvalidValue;  // lin_off is an offset here
     const bool nt = t.nontemporal && !a.host_tier;
     hipLaunchKernelGGL(nt ? xfer_quant_kernel<true> : xfer_quant_kernel<false>, dim3(a.grid), dim3(kThreads), 0, stream, a);
     return hipGetLastError();

@@ -3,7 +3,7 @@
 // row-relative tile rule and the plan the host makes.
 //
 // A wave walks a contiguous tile range, as in xfer_quant_kernel. Entering an op it
-// finds the row and piece of its first tile there (quant_strided_locate: the only
+// finds the row and piece of its first tile there (list_locate of ocm/list.h: the only
 // divide, skipped for rows of one tile) and counts from then on. Each tile is located
 // by the shared rule (quant_strided_tile) and then encoded or decoded by the tile
 // bodies the converting kernel uses (quant_tile.h). Everything but the lane's own
@@ -19,8 +19,6 @@
 #include "xfer_host.h"
 
 namespace ocm {
-
-static_assert(sizeof(XferQuantStridedArgs::ext) == sizeof(XferBatchArgs::ext), "extent table of a pair");
 
 namespace {
 
@@ -59,47 +57,15 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_strided_kernel(XferQuantS
     uint32_t k = 0;
     for (; t < t1; t++) {
         if (t >= next) {  // the wave's first tile, or the op's tiles are done: enter the op of tile t
-            for (;;) {
-                next = i + 1 < a.n_ops ? uniform64(ops[i + 1].first_tile) : ~0ull;
-                if (next > t) break;
-                i++;
-            }
+            next = list_enter_op(ops, a.n_ops, t, &i, ListLoadUniform());
             op = load_op(ops + i);
-            quant_strided_locate(op, t - op.first_tile, &row, &k);
+            list_locate(op.tiles_per_row, t - op.first_tile, &row, &k);
             row = uniform64(row);
             k = uniform32(k);
         }
-        const uint32_t cs = quant_code_shift(op.dtype);  // elements per code byte, log2
-        const QuantTileLoc q = quant_strided_tile(op, row, k, cs);
-        char *lin = a.lin + q.lin_off;
-        const bool bf16 = (op.dtype & kQuantElemMask) == kMx8Bf16;
-        if (cs) {
-            if (op.put) {
-                if (bf16)
-                    put_tile_mx4<true, PUT_NT>(a, lin, q.codes, q.scales, q.ne, lane, scale_lds[wl]);
-                else
-                    put_tile_mx4<false, PUT_NT>(a, lin, q.codes, q.scales, q.ne, lane, scale_lds[wl]);
-            } else {
-                if (bf16)
-                    get_tile_mx4<true>(a, lin, q.codes, q.scales, q.ne, lane);
-                else
-                    get_tile_mx4<false>(a, lin, q.codes, q.scales, q.ne, lane);
-            }
-        } else if (op.put) {
-            if (bf16)
-                put_tile<true, PUT_NT>(a, lin, q.codes, q.scales, q.ne, lane, scale_lds[wl]);
-            else
-                put_tile<false, PUT_NT>(a, lin, q.codes, q.scales, q.ne, lane, scale_lds[wl]);
-        } else {
-            if (bf16)
-                get_tile<true>(a, lin, q.codes, q.scales, q.ne, lane);
-            else
-                get_tile<false>(a, lin, q.codes, q.scales, q.ne, lane);
-        }
-        if (++k == op.tiles_per_row) {
-            k = 0;
-            row++;
-        }
+        const QuantTileLoc q = quant_strided_tile(op, row, k, quant_code_shift(op.dtype));  // log2(elements per code byte)
+        quant_tile<PUT_NT>(a, a.lin + q.lin_off, q.codes, q.scales, q.ne, op.dtype, op.put, lane, scale_lds[wl]);
+        list_next_piece(op.tiles_per_row, &row, &k);
     }
 }
 
@@ -107,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void xfer_quant_strided_kernel(XferQuantS
 
 hipError_t xfer_quant_strided_launch(const XferQuantStridedArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (!kernels::list_args_valid<true, false>(a, kQuantStridedInlineOps) || !a.lin) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<true>(a) || !a.lin) return hipErrorInvalidValue;
     const bool nt = t.nontemporal && !a.host_tier;
     hipLaunchKernelGGL(nt ? xfer_quant_strided_kernel<true> : xfer_quant_strided_kernel<false>, dim3(a.grid), dim3(kThreads), 0,
                        stream, a);

@@ -3,11 +3,12 @@
 // geometry and the plan the host makes.
 //
 // A wave walks a contiguous tile range, as in xfer_batch_kernel. Entering an op it
-// finds the row and piece of its first tile there (strided_locate: the only divide,
-// skipped for rows of one tile) and counts from then on. Each tile is one or two
-// spans (strided_row_pieces), each inside one stripe unit, copied by the shared
-// copy loop. Everything but the lane's own vectors is wave-uniform: the descriptor
-// is read through scalar loads, from the kernel arguments for short lists.
+// finds the row and piece of its first tile there (list_locate of ocm/list.h: the
+// only divide, skipped for rows of one tile) and counts from then on. Each tile is
+// one or two spans (strided_row_pieces), each inside one stripe unit, copied by the
+// shared copy loop (copy_piece of xfer_copy.h). Everything but the lane's own vectors
+// is wave-uniform: the descriptor is read through scalar loads, from the kernel
+// arguments for short lists.
 #include <hip/hip_runtime.h>
 
 #include "ocm/strided.h"
@@ -17,30 +18,7 @@
 
 namespace ocm {
 
-static_assert(sizeof(XferStridedArgs::ext) == sizeof(XferBatchArgs::ext), "extent table of a pair");
-
 namespace {
-
-constexpr int kStridedUnroll = 4;  // 64 lanes x 16 B x 4 in flight: one 4 KiB wave-tile a round
-
-template <bool NT>
-using WaveCopy = CopyCfg<64, kStridedUnroll, PointerAccess<NT>>;
-
-// One span, inside one stripe unit. HOST: every extent is pinned host memory; puts
-// store plain there, as the batch kernel's do.
-template <bool NT, bool HOST>
-__device__ __forceinline__ void copy_piece(const XferStridedArgs &a, const StridedPiece &p, uint32_t put) {
-    char *lp = a.lin + p.lin_off;
-    char *rp = stripe_ptr(a, a.n_ext, a.unit_shift, p.rem_off);
-    if (put) {
-        if (HOST)
-            copy_span<WaveCopy<false>>(rp, lp, p.n);
-        else
-            copy_span<WaveCopy<NT>>(rp, lp, p.n);
-    } else {
-        copy_span<WaveCopy<NT>>(lp, rp, p.n);
-    }
-}
 
 // The descriptor of an op, in scalar registers (uniform32 / uniform64, xfer_copy.h).
 __device__ __forceinline__ XferStridedOp load_op(const XferStridedOp *p) {
@@ -71,13 +49,9 @@ __global__ __launch_bounds__(kThreads) void xfer_strided_kernel(XferStridedArgs 
     uint64_t row = 0, k = 0; // tile t is piece k of row `row`
     for (; t < t1; t++) {
         if (t >= next) {  // the wave's first tile, or the op's tiles are done: enter the op of tile t
-            for (;;) {
-                next = i + 1 < a.n_ops ? uniform64(ops[i + 1].first_tile) : ~0ull;
-                if (next > t) break;
-                i++;
-            }
+            next = list_enter_op(ops, a.n_ops, t, &i, ListLoadUniform());
             op = load_op(ops + i);
-            strided_locate(op, t - op.first_tile, &row, &k);
+            list_locate(op.tiles_per_row, t - op.first_tile, &row, &k);
             row = uniform64(row);
             k = uniform64(k);
         }
@@ -85,10 +59,7 @@ __global__ __launch_bounds__(kThreads) void xfer_strided_kernel(XferStridedArgs 
         const int np = strided_row_pieces(op, row, k, a.n_ext, a.unit_shift, a.tile_shift, p);
         copy_piece<NT, HOST>(a, p[0], op.put);
         if (np == 2) copy_piece<NT, HOST>(a, p[1], op.put);
-        if (++k == op.tiles_per_row) {
-            k = 0;
-            row++;
-        }
+        list_next_piece(op.tiles_per_row, &row, &k);
     }
 }
 
@@ -96,9 +67,7 @@ __global__ __launch_bounds__(kThreads) void xfer_strided_kernel(XferStridedArgs 
 
 hipError_t xfer_strided_launch(const XferStridedArgs &a, const XferTuning &t, hipStream_t stream) {
     if (a.total_tiles == 0 || a.n_ops == 0) return hipSuccess;
-    if (!kernels::list_args_valid<false, false>(a, kStridedInlineOps) || !a.lin) return hipErrorInvalidValue;
-    // a tile is at most one stripe unit (two spans a tile at the most)
-    if (a.tile_shift > 63 || (a.n_ext > 1 && a.tile_shift > a.unit_shift)) return hipErrorInvalidValue;
+    if (!kernels::list_args_valid<false>(a) || !kernels::list_tile_fits_unit(a) || !a.lin) return hipErrorInvalidValue;
     auto kernel = a.host_tier    ? xfer_strided_kernel<true, true>
                   : t.nontemporal ? xfer_strided_kernel<true, false>
                                   : xfer_strided_kernel<false, false>;

@@ -59,31 +59,33 @@ int list_call(const ListNames &k, const uint64_t &traced, Impl impl, Count count
     });
 }
 
-// The plan's side of launch arguments whose pair's side is set: the descriptors `v`
-// planned by plan(ops, n, tile_shift) (first_tile filled in), the grid, and the
-// descriptors themselves when they travel in the kernel arguments.
-template <class Args, class Op, class Plan>
-void list_plan_args(Args *args, std::vector<Op> &v, Plan plan) {
+// The plan's side of launch arguments (the head every kind shares, ocm/list.h) whose
+// pair's side is set: the descriptors `v` planned by plan(ops, n, tile_shift) (first_tile
+// filled in), the grid, and the descriptors themselves when they travel in the kernel
+// arguments.
+template <class Op, int INLINE, class Plan>
+void list_plan_args(ListArgs<Op, INLINE> *args, std::vector<Op> &v, Plan plan) {
     args->n_ops = (uint32_t)v.size();
     args->total_tiles = plan(v.data(), (uint32_t)v.size(), args->tile_shift);
     args->grid = args->total_tiles ? xfer_batch_grid(args->total_tiles, args->host_tier != 0) : 0;
-    if (v.size() <= sizeof(args->inline_ops) / sizeof(Op)) std::memcpy(args->inline_ops, v.data(), v.size() * sizeof(Op));
+    if (v.size() <= (size_t)INLINE) std::memcpy(args->inline_ops, v.data(), v.size() * sizeof(Op));
 }
 
-// Launch arguments of a list on `a`: the pair's side (the linear base, the extents and
-// how they stripe), then the plan's (list_plan_args). elem_shift: the tile shift of a
-// kind that cuts tiles in elements; 0: byte tiles, xfer_batch_tile_shift of the pair.
-// -1: the pair's stripe unit is unusable (the error is set).
-template <class Args, class Op, class Plan>
-int list_fill_args(lib_alloc *a, std::vector<Op> &v, uint32_t elem_shift, Plan plan, Args *args) {
+// Launch arguments of a list on `a`: a kind's `Args` (the head, or a struct derived from
+// it) zeroed, the kind's own fields included; then the head's pair side (the linear base,
+// the extents and how they stripe) and its plan side (list_plan_args). elem_shift: the tile
+// shift of a kind that cuts tiles in elements; 0: byte tiles, xfer_batch_tile_shift of the
+// pair. -1: the pair's stripe unit is unusable (the error is set).
+template <class Args, class Plan>
+int list_fill_args(lib_alloc *a, std::vector<typename Args::Op> &v, uint32_t elem_shift, Plan plan, Args *args) {
     std::memset(args, 0, sizeof(*args));
-    args->lin = static_cast<char *>(a->local);
-    static_assert(sizeof(args->ext) / sizeof(args->ext[0]) == kXferMaxExtents, "extent table of a pair");
-    if (pair_side(a, 0, args) < 0)
+    ListArgs<typename Args::Op, Args::kInline> *head = args;
+    head->lin = static_cast<char *>(a->local);
+    if (pair_side(a, 0, head) < 0)
         OCM_FAIL(-1, "stripe unit %llu is not a power of two", (unsigned long long)a->stripe_unit);
-    args->host_tier = (!a->any_gpu && !a->any_net) ? 1u : 0u;
-    args->tile_shift = elem_shift ? elem_shift : xfer_batch_tile_shift(args->n_ext, args->unit_shift);
-    list_plan_args(args, v, plan);
+    head->host_tier = (!a->any_gpu && !a->any_net) ? 1u : 0u;
+    head->tile_shift = elem_shift ? elem_shift : xfer_batch_tile_shift(head->n_ext, head->unit_shift);
+    list_plan_args(head, v, plan);
     return 0;
 }
 
@@ -94,8 +96,8 @@ size_t list_upload_bytes(size_t n_ops, uint32_t grid) {
 }
 // Packs it into `up` (list_upload_bytes long) and points `args` at where it will lie in
 // device memory, `dev`.
-template <class Args, class Op>
-void list_pack(Args *args, const std::vector<Op> &v, void *up, void *dev) {
+template <class Op, int INLINE>
+void list_pack(ListArgs<Op, INLINE> *args, const std::vector<Op> &v, void *up, void *dev) {
     const size_t dbytes = v.size() * sizeof(Op);
     std::memcpy(up, v.data(), dbytes);
     list_wave_ops(v.data(), (uint32_t)v.size(), args->total_tiles, args->grid,
@@ -111,7 +113,7 @@ int list_staging(lib_alloc *a, size_t need, hipStream_t st);
 // Upload (large lists), launch and complete one planned list on `a`: the staging buffer,
 // its batch_up event and the completion every kind shares. n_launches: counted after a
 // launch (batches count n_batch_launches).
-template <class Args, class Op>
+template <class Args, class Op = typename Args::Op>
 int run_list(lib_alloc *a, Args &args, const std::vector<Op> &v,
              hipError_t (*launch)(const Args &, const XferTuning &, hipStream_t), bool async, uint64_t *n_launches = nullptr) {
     State &s = S();
@@ -120,7 +122,7 @@ int run_list(lib_alloc *a, Args &args, const std::vector<Op> &v,
     hipStream_t st = async ? lane_stream(a) : s.stream;
     if (honor_dep(a, st, false) != 0) return -1;
     hipError_t err = hipSuccess;
-    if (v.size() > sizeof(args.inline_ops) / sizeof(Op)) {
+    if (v.size() > (size_t)Args::kInline) {
         const size_t need = list_upload_bytes<Op>(v.size(), args.grid);
         if (list_staging(a, need, st) != 0) return -1;
         list_pack(&args, v, a->batch_host, a->batch_dev);

@@ -226,7 +226,7 @@ void test_walk() {
                     if (t >= t1) continue;
                     CHECK(t1 <= total, "wave range past the tiles");
                     uint64_t j, k;
-                    indexed_locate(tpr, t, &j, &k);
+                    list_locate(tpr, t, &j, &k);
                     for (; t < t1; t += kAdamRowsInFlight)
                         for (int u = 0; u < kAdamRowsInFlight && t + u < t1; u++) {
                             CHECK(j < rows && k < tpr && j * tpr + k == t + u, "tile %llu is not (%llu, %llu)",

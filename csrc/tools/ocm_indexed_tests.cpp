@@ -49,7 +49,7 @@ void check_op(XferIndexedOp op, const std::vector<int64_t> &lidx, const std::vec
     for (int wv = 0; wv < 3; wv++) {
         uint64_t j = 0, k = 0, lr = 0, rr = 0;
         bool enter = true, ok = false;
-        if (cuts[wv] < cuts[wv + 1]) indexed_locate(op.tiles_per_row, cuts[wv], &j, &k);
+        if (cuts[wv] < cuts[wv + 1]) list_locate(op.tiles_per_row, cuts[wv], &j, &k);
         for (uint64_t t = cuts[wv]; t < cuts[wv + 1]; t++) {
             CHECK(j == t / op.tiles_per_row && k == t % op.tiles_per_row, "tile %llu is not row %llu piece %llu",
                   (unsigned long long)t, (unsigned long long)j, (unsigned long long)k);
@@ -85,11 +85,7 @@ void check_op(XferIndexedOp op, const std::vector<int64_t> &lidx, const std::vec
                     CHECK((p[1].rem_off & ((1ull << L.unit_shift) - 1)) == 0, "second piece not at a unit boundary");
                 }
             }
-            if (++k == op.tiles_per_row) {
-                k = 0;
-                j++;
-                enter = true;
-            }
+            if (list_next_piece(op.tiles_per_row, &j, &k)) enter = true;
         }
     }
     for (uint32_t j = 0; j < op.rows; j++) {

@@ -1,7 +1,9 @@
 // The plan every descriptor list shares (ocm/list.h: list_plan, list_wave_ops,
 // list_wave_range) under each kind's tile-count rule, as the library calls it
 // (xfer_batch_plan, xfer_quant_plan, xfer_strided_plan, acc_plan), against a brute-force
-// walk of every tile. Stand-alone: it links nothing of the library, so the build also
+// walk of every tile; and the walk the row kernels make through a list (list_enter_op,
+// list_locate, list_next_piece: the functions they call) against the enumeration of its
+// ops, rows and pieces. Stand-alone: it links nothing of the library, so the build also
 // makes an ASan + UBSan copy of it.
 #include <cstdio>
 #include <vector>
@@ -88,12 +90,18 @@ void check_list(const char *kind, const std::vector<Op> &v, uint64_t total, cons
             const Op &op = v[start[w]];
             CHECK(op.first_tile <= t0 && t0 < op.first_tile + tiles[start[w]], "%s: wave %u of grid %u (tile %llu) starts in op %u",
                   kind, w, grid, (unsigned long long)t0, start[w]);
-            // the kernels' walk from there finds the op of every tile of the range
-            uint32_t i = start[w];
+            // the kernels' walks from there find the op of every tile of the range: the advance of
+            // the kernels without rows, and list_enter_op as the row kernels call it
+            uint32_t i = start[w], ir = start[w];
+            uint64_t next = 0;
             for (uint64_t t = t0; t < t1; t++) {
                 while (i + 1 < n && v[i + 1].first_tile <= t) i++;
-                CHECK(i == op_of[(size_t)t], "%s: grid %u tile %llu: the walk is in op %u, the tile belongs to op %u", kind, grid,
-                      (unsigned long long)t, i, op_of[(size_t)t]);
+                if (t >= next) next = list_enter_op(v.data(), n, t, &ir);
+                CHECK(i == op_of[(size_t)t] && ir == i, "%s: grid %u tile %llu: the walks are in ops %u and %u, the tile belongs to op %u",
+                      kind, grid, (unsigned long long)t, i, ir, op_of[(size_t)t]);
+                CHECK(next > t && (ir + 1 == n ? next == ~0ull : next == v[ir + 1].first_tile),
+                      "%s: grid %u tile %llu: the op after op %u is said to start at %llu", kind, grid, (unsigned long long)t, ir,
+                      (unsigned long long)next);
                 owners[(size_t)t]++;
             }
         }
@@ -192,6 +200,86 @@ void test_strided() {
         });
 }
 
+// The walk of the kernels whose ops have rows, by the functions they call (list_enter_op,
+// list_locate, list_next_piece), as a wave makes it: for every wave of a grid, the (op, row,
+// piece) of each of its tiles, against the enumeration of ops, rows and pieces in order.
+// K: the width the kernel keeps the piece number in (the converting kernel: 32 bits).
+// Rows of 1, 2 and 3 tiles, ops of 0, 1 and 3 rows and small grids make waves start
+// mid-row and mid-op and cross empty ops.
+template <class K>
+void row_walk(const std::vector<XferStridedOp> &v, uint64_t total, int *walked) {
+    struct Tile {
+        uint32_t op;
+        uint64_t row, k;
+    };
+    const uint32_t n = (uint32_t)v.size();
+    std::vector<Tile> want;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint64_t r = 0; r < v[i].rows; r++)
+            for (uint64_t k = 0; k < v[i].tiles_per_row; k++) want.push_back(Tile{i, r, k});
+    CHECK(want.size() == total, "row_walk: %zu tiles enumerated, the plan has %llu", want.size(), (unsigned long long)total);
+    if (want.size() != total) return;
+    for (uint32_t grid : {1u, 2u, 5u}) {
+        const uint32_t waves = grid * kListWaves;
+        std::vector<uint32_t> start(waves);
+        list_wave_ops(v.data(), n, total, grid, start.data());
+        uint64_t seen = 0;
+        for (uint32_t w = 0; w < waves; w++) {
+            uint64_t t, t1;
+            list_wave_range(w, grid, total, &t, &t1);
+            if (t >= t1) continue;
+            CHECK(t == seen, "row_walk: wave %u of grid %u starts at tile %llu, not %llu", w, grid, (unsigned long long)t,
+                  (unsigned long long)seen);
+            uint32_t i = start[w];
+            uint64_t next = 0, row = 0;
+            K k = 0;
+            for (; t < t1; t++, seen++) {
+                if (t >= next) {  // as the kernels enter an op
+                    next = list_enter_op(v.data(), n, t, &i);
+                    list_locate(v[i].tiles_per_row, t - v[i].first_tile, &row, &k);
+                }
+                const Tile &x = want[(size_t)t];
+                CHECK(i == x.op && row == x.row && k == x.k,
+                      "row_walk: grid %u wave %u tile %llu of %u ops: the walk says (%u, %llu, %llu), the enumeration (%u, %llu, %llu)",
+                      grid, w, (unsigned long long)t, n, i, (unsigned long long)row, (unsigned long long)k, x.op,
+                      (unsigned long long)x.row, (unsigned long long)x.k);
+                const bool new_row = list_next_piece((K)v[i].tiles_per_row, &row, &k);
+                CHECK(new_row == (x.k + 1 == v[i].tiles_per_row), "row_walk: tile %llu: a new row after piece %llu of %llu",
+                      (unsigned long long)t, (unsigned long long)x.k, (unsigned long long)v[i].tiles_per_row);
+                (*walked)++;
+            }
+        }
+        CHECK(seen == total, "row_walk: grid %u: the waves walked %llu of %llu tiles", grid, (unsigned long long)seen,
+              (unsigned long long)total);
+    }
+}
+
+void test_row_walk() {
+    const int before = failures;
+    const uint32_t shift = 12, kRows[] = {0, 1, 3};
+    int walked = 0;
+    for (uint32_t n : kCounts)
+        for (int variant = 0; variant < 4; variant++)
+            for (uint32_t phase = 0; phase < 9; phase++) {  // every (tiles_per_row, rows) pair in every place of the list
+                std::vector<XferStridedOp> v(n, XferStridedOp{});
+                for (uint32_t i = 0; i < n; i++) {
+                    const uint32_t tpr = 1 + (i + phase) % 3, rows = forced_empty(variant, i, n) ? 0 : kRows[(i + phase) / 3 % 3];
+                    v[i].rows = rows;
+                    v[i].row_bytes = rows ? ((uint64_t)tpr << shift) - 48 : 0;  // the last piece of a row is partial
+                    v[i].lin_stride = v[i].rem_stride = v[i].row_bytes;
+                }
+                const uint64_t total = xfer_strided_plan(v.data(), n, shift);
+                for (uint32_t i = 0; i < n; i++)
+                    CHECK(v[i].tiles_per_row == (v[i].rows ? 1 + (i + phase) % 3 : 0), "row_walk: op %u has %llu tiles a row", i,
+                          (unsigned long long)v[i].tiles_per_row);
+                row_walk<uint64_t>(v, total, &walked);
+                row_walk<uint32_t>(v, total, &walked);
+            }
+    CHECK(walked > 100000, "row_walk: only %d tiles walked", walked);
+    std::printf("row_walk: %d tiles walked\n", walked);
+    if (failures == before) std::printf("PASS row_walk\n");
+}
+
 // list_wave_range on its own: the ranges tile [0, total) in wave order, with fewer tiles
 // than waves and with totals that are no multiple of the wave count.
 void test_wave_range() {
@@ -232,6 +320,7 @@ int main() {
     test_quant();
     test_strided();
     test_acc();
+    test_row_walk();
     test_wave_range();
     std::printf("%d failure(s)\n", failures);
     return failures ? 1 : 0;

@@ -214,7 +214,7 @@ void strided_tile_location() {
         for (uint64_t t = 0; t < total; t++) {
             uint64_t row;
             uint32_t k;
-            quant_strided_locate(op, t, &row, &k);
+            list_locate(op.tiles_per_row, t, &row, &k);
             const QuantTileLoc q = quant_strided_tile(op, row, k, cs);
             const uint64_t rec = p.remote_offset + row * p.remote_stride, e0 = (uint64_t)k << kQuantTileShift;
             check(q.lin_off == p.local_offset + row * p.local_stride + 2 * e0, "strided", "elements of tile", (long)t, (unsigned)q.lin_off, 0);

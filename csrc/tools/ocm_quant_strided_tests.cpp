@@ -61,7 +61,7 @@ void check_op(XferQuantStridedOp op, uint64_t *tiles_seen) {
     for (uint64_t t = 0; t < total; t++) {
         uint64_t row;
         uint32_t k;
-        quant_strided_locate(op, t, &row, &k);
+        list_locate(op.tiles_per_row, t, &row, &k);
         CHECK(row == t / op.tiles_per_row && k == t % op.tiles_per_row, "tile %llu located at row %llu piece %u", (ull)t,
               (ull)row, k);
         const QuantTileLoc q = quant_strided_tile(op, row, k, 0);  // MXFP8: one code byte per element
@@ -88,16 +88,10 @@ void check_op(XferQuantStridedOp op, uint64_t *tiles_seen) {
     for (uint64_t start : {(uint64_t)0, total / 3, total - 1}) {
         uint64_t row;
         uint32_t k;
-        quant_strided_locate(op, start, &row, &k);
+        list_locate(op.tiles_per_row, start, &row, &k);
         for (uint64_t t = start; t < total; t++) {
-            uint64_t row2;
-            uint32_t k2;
-            quant_strided_locate(op, t, &row2, &k2);
-            CHECK(row == row2 && k == k2, "walk differs at tile %llu", (ull)t);
-            if (++k == op.tiles_per_row) {
-                k = 0;
-                row++;
-            }
+            CHECK(row == t / op.tiles_per_row && k == t % op.tiles_per_row, "walk differs at tile %llu", (ull)t);
+            list_next_piece(op.tiles_per_row, &row, &k);
         }
     }
 }

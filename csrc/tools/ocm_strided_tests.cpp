@@ -33,7 +33,7 @@ struct Layout {
 
 // Every tile of `op`: the pieces partition each row exactly once, stay inside the row,
 // keep both sides at the same offset in the row, and never cross a stripe unit. Then
-// the walk the kernel makes (locate once, count afterwards) from several first tiles.
+// the walk the kernel makes (list_locate once, list_next_piece afterwards) from several first tiles.
 void check_op(XferStridedOp op, const Layout &L, uint64_t *pieces_seen, uint64_t *split_seen) {
     const uint64_t total = xfer_strided_plan(&op, 1, L.tile_shift);
     CHECK(op.first_tile == 0 && total == (uint64_t)op.rows * strided_tiles_per_row(op.row_bytes, L.tile_shift), "plan");
@@ -46,7 +46,7 @@ void check_op(XferStridedOp op, const Layout &L, uint64_t *pieces_seen, uint64_t
         StridedPiece p[2];
         const int np = strided_tile_pieces(op, t, L.n_ext, L.unit_shift, L.tile_shift, p);
         CHECK(np == 1 || np == 2, "tile %llu: %d pieces", (unsigned long long)t, np);
-        const uint64_t row = t / op.tiles_per_row;  // the issue's rule, worked out apart from strided_locate
+        const uint64_t row = t / op.tiles_per_row;  // the issue's rule, worked out apart from list_locate
         const uint64_t l0 = op.lin_off + row * op.lin_stride, r0 = op.rem_off + row * op.rem_stride;
         uint64_t tile_bytes = 0;
         for (int j = 0; j < np; j++) {
@@ -75,20 +75,18 @@ void check_op(XferStridedOp op, const Layout &L, uint64_t *pieces_seen, uint64_t
     for (uint8_t c : cover) bad += c != 1;
     CHECK(bad == 0, "%zu bytes not moved exactly once (rows %u x %llu, unit 2^%u, tile 2^%u, n_ext %u, rem_off %llu)", bad,
           op.rows, (unsigned long long)op.row_bytes, L.unit_shift, L.tile_shift, L.n_ext, (unsigned long long)op.rem_off);
-    // the kernel's walk: strided_locate at a wave's first tile, then k / row counted up
+    // the kernel's walk, by the functions it calls (ocm/list.h): list_locate at a wave's first
+    // tile, then list_next_piece
     for (uint64_t start : {(uint64_t)0, total / 3, total - 1}) {
         uint64_t row, k;
-        strided_locate(op, start, &row, &k);
+        list_locate(op.tiles_per_row, start, &row, &k);
         for (uint64_t t = start; t < total; t++) {
             StridedPiece a[2], b[2];
             const int na = strided_row_pieces(op, row, k, L.n_ext, L.unit_shift, L.tile_shift, a);
             const int nb = strided_tile_pieces(op, t, L.n_ext, L.unit_shift, L.tile_shift, b);
             CHECK(na == nb && std::memcmp(a, b, sizeof(StridedPiece) * (size_t)na) == 0, "walk differs at tile %llu",
                   (unsigned long long)t);
-            if (++k == op.tiles_per_row) {
-                k = 0;
-                row++;
-            }
+            list_next_piece(op.tiles_per_row, &row, &k);
         }
     }
 }

@@ -21,25 +21,14 @@ def test_validator_rules_walk_and_shape(native, tool, binary):
 
 def test_rows_kernel_uses_no_scratch_no_vector_spills_and_no_lds():
     # as tests/test_indexed_native.py does for the indexed kernel: the compiler's resource report
-    import os
-    import re
-    import subprocess
+    from kernel_report import kernel_report
 
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{repo}/csrc/include",
-                        "-c", f"{repo}/csrc/src/kernels/optim_rows.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    vspills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
+    k = kernel_report("optim_rows.hip")
+    names = k.column("name")
     # two instantiations, by table dtype: the index type is a branch, not a template parameter
     assert len(names) == 2 and all("adam_rows_kernel" in n for n in names), names
-    assert len(scratch) == len(vspills) == len(lds) == 2
-    assert all(s == 0 for s in scratch), dict(zip(names, scratch))
-    assert all(s == 0 for s in vspills), dict(zip(names, vspills))
-    assert all(s == 0 for s in lds), dict(zip(names, lds))
+    for key in ("scratch", "vgpr_spills", "lds"):
+        assert all(v == 0 for v in k.column(key)), dict(zip(names, k.column(key)))
 
 
 def test_registered_with_ctest(native, tool):

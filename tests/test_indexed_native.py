@@ -20,27 +20,14 @@ def test_geometry_bounds_validator_and_plan(native, tool, binary):
 
 def test_indexed_kernel_uses_no_scratch_no_spills_and_no_lds():
     # as tests/test_strided_native.py does for the strided kernel: the compiler's resource report
-    import os
-    import re
-    import subprocess
+    from kernel_report import kernel_report
 
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{repo}/csrc/include",
-                        "-c", f"{repo}/csrc/src/kernels/xfer_indexed.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    vspills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    sspills = [int(v) for v in re.findall(r"SGPRs Spill: (\d+)", r.stderr)]
-    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
+    k = kernel_report("xfer_indexed.hip")
+    names = k.column("name")
     # three instantiations, as the strided kernel has: the index type is a branch, not a template parameter
     assert len(names) == 3 and all("xfer_indexed_kernel" in n for n in names), names
-    assert len(scratch) == len(vspills) == len(sspills) == len(lds) == 3
-    assert all(s == 0 for s in scratch), dict(zip(names, scratch))
-    assert all(s == 0 for s in vspills), dict(zip(names, vspills))
-    assert all(s == 0 for s in sspills), dict(zip(names, sspills))
-    assert all(s == 0 for s in lds), dict(zip(names, lds))
+    for key in ("scratch", "vgpr_spills", "sgpr_spills", "lds"):
+        assert all(v == 0 for v in k.column(key)), dict(zip(names, k.column(key)))
 
 
 def test_registered_with_ctest(native, tool):

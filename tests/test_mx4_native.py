@@ -3,16 +3,12 @@ strided location of MXFP4 tiles (csrc/include/ocm/quant_strided.h): the stand-al
 csrc/tools/ocm_mx4_tests.cpp, as built and as built with ASan + UBSan (host code only, run
 directly: nothing is preloaded and nothing is loaded into Python). And the compiler's resource
 report of both converting kernels, which now hold the MXFP4 tile bodies too."""
-import os
-import re
-import subprocess
-
 import pytest
+from kernel_report import kernel_report
 
 from oncilla_amd.utils.paths import BUILD_DIR
 
 PARTS = ("edge_groups", "amax_sweep", "e2m1_codes", "record_layout", "strided_tile_location")
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("binary", ["ocm_mx4_tests", "ocm_mx4_tests_asan"])
@@ -34,16 +30,11 @@ def test_registered_with_ctest(native, tool):
 def test_kernels_hold_the_fp4_converts_and_use_no_scratch(kernel):
     # the MXFP4 bodies are inlined into the two kernels of each file: the packed fp4 converts are in
     # their code, and they still use no scratch, spill nothing and keep 64 scale bytes of LDS per wave
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{REPO}/csrc/include",
-                        "-S", "--cuda-device-only", f"{REPO}/csrc/src/kernels/{kernel}.hip", "-o", "-",
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    assert len(names) == 2, names
-    for key in (r"ScratchSize \[bytes/lane\]", "VGPRs Spill", "SGPRs Spill"):
-        vals = [int(v) for v in re.findall(key + r": (\d+)", r.stderr)]
-        assert vals == [0, 0], (key, vals)
-    assert [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)] == [256, 256]
+    k = kernel_report(f"{kernel}.hip", emit="asm")
+    assert len(k) == 2, k.column("name")
+    for key in ("scratch", "vgpr_spills", "sgpr_spills"):
+        assert k.column(key) == [0, 0], (key, k.column(key))
+    assert k.column("lds") == [256, 256]
     for insn in ("v_cvt_scalef32_pk_fp4_bf16", "v_cvt_scalef32_pk_fp4_f16", "v_cvt_scalef32_pk_bf16_fp4",
                  "v_cvt_scalef32_pk_f16_fp4"):
-        assert r.stdout.count(insn) >= 8, (insn, r.stdout.count(insn))  # four per tile body, two kernels
+        assert k.asm.count(insn) >= 8, (insn, k.asm.count(insn))  # four per tile body, two kernels

@@ -31,21 +31,13 @@ def test_kernels_use_no_scratch(src, min_kernels):
     # Resource check of every gfx950 kernel: a dynamically indexed local array
     # (e.g. a copied extent table) lands in scratch and costs a memory round
     # trip per access on the hot path. The compiler reports it per kernel.
-    import os
-    import re
-    import subprocess
+    from kernel_report import kernel_report
 
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                        f"-I{repo}/csrc/include", "-c", f"{repo}/csrc/src/kernels/{src}", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    assert len(names) >= min_kernels and len(scratch) == len(names)
-    assert all(s == 0 for s in scratch), dict(zip(names, scratch))
-    assert all(s == 0 for s in spills), dict(zip(names, spills))
+    k = kernel_report(src)
+    names = k.column("name")
+    assert len(names) >= min_kernels
+    for key in ("scratch", "vgpr_spills"):
+        assert all(v == 0 for v in k.column(key)), dict(zip(names, k.column(key)))
 
 
 def test_example_nodefiles_parse(native, tool):

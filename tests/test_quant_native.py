@@ -20,21 +20,13 @@ def test_host_codec_vectors(native, tool, binary):
 def test_quant_kernel_uses_no_scratch():
     # as tests/test_native_unit.py does for the other kernels: the extent table is indexed
     # per lane here, which must stay a load from the kernel arguments, never a scratch copy
-    import os
-    import re
-    import subprocess
+    from kernel_report import kernel_report
 
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{repo}/csrc/include",
-                        "-c", f"{repo}/csrc/src/kernels/xfer_quant.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    assert len(names) >= 2 and len(scratch) == len(names)
-    assert all(s == 0 for s in scratch), dict(zip(names, scratch))
-    assert all(s == 0 for s in spills), dict(zip(names, spills))
+    k = kernel_report("xfer_quant.hip")
+    names = k.column("name")
+    assert len(names) >= 2
+    for key in ("scratch", "vgpr_spills"):
+        assert all(v == 0 for v in k.column(key)), dict(zip(names, k.column(key)))
 
 
 def test_registered_with_ctest(native, tool):

@@ -20,23 +20,13 @@ def test_tile_geometry_and_validator(native, tool, binary):
 
 def test_strided_kernel_uses_no_scratch_and_no_lds():
     # as tests/test_quant_native.py does for the converting kernel: the compiler's resource report
-    import os
-    import re
-    import subprocess
+    from kernel_report import kernel_report
 
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{repo}/csrc/include",
-                        "-c", f"{repo}/csrc/src/kernels/xfer_strided.hip", "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
-    assert len(names) == 3 and len(scratch) == len(names) == len(lds)
-    assert all(s == 0 for s in scratch), dict(zip(names, scratch))
-    assert all(s == 0 for s in spills), dict(zip(names, spills))
-    assert all(s == 0 for s in lds), dict(zip(names, lds))
+    k = kernel_report("xfer_strided.hip")
+    names = k.column("name")
+    assert len(names) == 3
+    for key in ("scratch", "vgpr_spills", "lds"):
+        assert all(v == 0 for v in k.column(key)), dict(zip(names, k.column(key)))
 
 
 def test_registered_with_ctest(native, tool):
