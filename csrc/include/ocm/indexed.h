@@ -18,13 +18,16 @@
 // written them just before, and what orders the transfer after that kernel is
 // ocm_stream_wait, as for the rows themselves.
 //
-// Out of scope: transfer plans and hipGraph capture, the copy service, converting (MX)
-// and accumulate variants, index-times-stride (layer-major) ops, a defined result for
-// duplicate destination rows, and scatter-add.
+// Out of scope: transfer plans and hipGraph capture, the copy service, accumulate
+// variants, index-times-stride (layer-major) ops, a defined result for duplicate
+// destination rows, and scatter-add. The converting (MX) variant is a call of its own,
+// ocm_copy_onesided_quant_indexed (ocm/quant_indexed.h), which shares the bounds rule, the
+// validator's helpers and the skip count of this one.
 //
 // This header is what the kernel (xfer_indexed.hip), the host side (indexed.cpp) and the
 // stand-alone test program (ocm_indexed_tests.cpp) share; it needs no HIP.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
@@ -78,29 +81,32 @@ inline uint64_t indexed_load_host(const char *base, uint64_t off, uint32_t index
     return indexed_widen32(v);
 }
 
-// One op against halves of local_bytes / remote_bytes. 0: fine (*moved = rows * row_bytes,
-// the nominal bytes; 0 for an empty op); -1: `why` says what is wrong. No sum or product
-// here can overflow: a table's last row is tested as stride <= (room left) / (rows - 1),
-// an index array as rows <= (room left) / element size.
-inline int indexed_check_op(const struct ocm_indexed_params &p, uint64_t local_bytes, uint64_t remote_bytes,
-                            uint64_t *moved, char *why, size_t why_len) {
-    *moved = 0;
-    if (p.rows == 0 || p.row_bytes == 0) return 0;  // does nothing, whatever else it says
-    if (p.index_type != OCM_INDEX_I32 && p.index_type != OCM_INDEX_I64) {
-        std::snprintf(why, why_len, "index_type %u is unknown (OCM_INDEX_I32 = 1, OCM_INDEX_I64 = 2)", p.index_type);
+// One side of an op as the checks below see it. row_bytes is per side: the indexed op
+// moves the same bytes on both, the converting one (ocm/quant_indexed.h) 16-bit elements
+// on the local side and a record on the remote one.
+struct IndexedSide {
+    const char *side;
+    uint64_t off, stride, size, table_rows, idx_off, row_bytes;
+};
+
+// index_type is known, and at least one side has an index. 0, or -1 with `why`.
+inline int indexed_check_kind(uint32_t index_type, uint64_t local_index_offset, uint64_t remote_index_offset, char *why,
+                              size_t why_len) {
+    if (index_type != OCM_INDEX_I32 && index_type != OCM_INDEX_I64) {
+        std::snprintf(why, why_len, "index_type %u is unknown (OCM_INDEX_I32 = 1, OCM_INDEX_I64 = 2)", index_type);
         return -1;
     }
-    if (p.local_index_offset == OCM_INDEX_NONE && p.remote_index_offset == OCM_INDEX_NONE) {
+    if (local_index_offset == OCM_INDEX_NONE && remote_index_offset == OCM_INDEX_NONE) {
         std::snprintf(why, why_len, "no index on either side (a strided op moves rows in order)");
         return -1;
     }
-    const struct {
-        const char *side;
-        uint64_t off, stride, size, table_rows, idx_off;
-    } sides[2] = {{"local", p.local_offset, p.local_stride, local_bytes, p.local_rows, p.local_index_offset},
-                  {"remote", p.remote_offset, p.remote_stride, remote_bytes, p.remote_rows, p.remote_index_offset}};
-    if (p.rows >= (1ull << 32)) {
-        std::snprintf(why, why_len, "%llu rows (fewer than 2^32 are needed)", (unsigned long long)p.rows);
+    return 0;
+}
+
+// rows and both tables' rows are below 2^32.
+inline int indexed_check_counts(uint64_t rows, const IndexedSide (&sides)[2], char *why, size_t why_len) {
+    if (rows >= (1ull << 32)) {
+        std::snprintf(why, why_len, "%llu rows (fewer than 2^32 are needed)", (unsigned long long)rows);
         return -1;
     }
     for (const auto &s : sides)
@@ -109,53 +115,86 @@ inline int indexed_check_op(const struct ocm_indexed_params &p, uint64_t local_b
                           (unsigned long long)s.table_rows);
             return -1;
         }
-    for (const auto &s : sides) {
-        if (s.table_rows > 1 && s.stride < p.row_bytes) {
-            std::snprintf(why, why_len, "%s stride %llu is below the row's %llu bytes (rows would overlap)", s.side,
-                          (unsigned long long)s.stride, (unsigned long long)p.row_bytes);
-            return -1;
-        }
-        // a table of no rows holds no byte: every index of that side is out of range
-        bool fits = s.table_rows == 0 || (s.off <= s.size && p.row_bytes <= s.size - s.off);
-        if (fits && s.table_rows > 1) fits = s.stride <= (s.size - s.off - p.row_bytes) / (s.table_rows - 1);
-        if (!fits) {
-            std::snprintf(why, why_len, "%s table [%llu, +%llu rows x %llu bytes, stride %llu) exceeds %llu bytes", s.side,
-                          (unsigned long long)s.off, (unsigned long long)s.table_rows, (unsigned long long)p.row_bytes,
-                          (unsigned long long)s.stride, (unsigned long long)s.size);
-            return -1;
-        }
-        if (s.idx_off == OCM_INDEX_NONE && s.table_rows < p.rows) {
-            std::snprintf(why, why_len, "%s side has no index and a table of %llu rows, fewer than the op's %llu", s.side,
-                          (unsigned long long)s.table_rows, (unsigned long long)p.rows);
+    return 0;
+}
+
+// The table of one side: rows do not overlap, its last row ends inside its half, and a
+// side without an index has a row for every row of the op. No sum or product here can
+// overflow: the last row is tested as stride <= (room left) / (rows - 1).
+inline int indexed_check_table(const IndexedSide &s, uint64_t rows, char *why, size_t why_len) {
+    if (s.table_rows > 1 && s.stride < s.row_bytes) {
+        std::snprintf(why, why_len, "%s stride %llu is below the row's %llu bytes (rows would overlap)", s.side,
+                      (unsigned long long)s.stride, (unsigned long long)s.row_bytes);
+        return -1;
+    }
+    // a table of no rows holds no byte: every index of that side is out of range
+    bool fits = s.table_rows == 0 || (s.off <= s.size && s.row_bytes <= s.size - s.off);
+    if (fits && s.table_rows > 1) fits = s.stride <= (s.size - s.off - s.row_bytes) / (s.table_rows - 1);
+    if (!fits) {
+        std::snprintf(why, why_len, "%s table [%llu, +%llu rows x %llu bytes, stride %llu) exceeds %llu bytes", s.side,
+                      (unsigned long long)s.off, (unsigned long long)s.table_rows, (unsigned long long)s.row_bytes,
+                      (unsigned long long)s.stride, (unsigned long long)s.size);
+        return -1;
+    }
+    if (s.idx_off == OCM_INDEX_NONE && s.table_rows < rows) {
+        std::snprintf(why, why_len, "%s side has no index and a table of %llu rows, fewer than the op's %llu", s.side,
+                      (unsigned long long)s.table_rows, (unsigned long long)rows);
+        return -1;
+    }
+    return 0;
+}
+
+// The index array of side `s` (it has one): aligned to its element size, `rows` entries
+// inside the local half, tested as rows <= (room left) / element size; and for a get,
+// which writes the local table `local` (checked by indexed_check_table already), outside
+// that table.
+inline int indexed_check_index_array(const IndexedSide &s, uint32_t index_type, uint64_t rows, uint64_t local_bytes, bool get,
+                                     const IndexedSide &local, char *why, size_t why_len) {
+    const uint64_t isz = indexed_index_bytes(index_type);
+    if (s.idx_off % isz) {
+        std::snprintf(why, why_len, "%s index offset %llu is not a multiple of the index size %llu", s.side,
+                      (unsigned long long)s.idx_off, (unsigned long long)isz);
+        return -1;
+    }
+    if (s.idx_off > local_bytes || rows > (local_bytes - s.idx_off) / isz) {
+        std::snprintf(why, why_len, "%s index array [%llu, +%llu x %llu bytes) exceeds the local half's %llu bytes", s.side,
+                      (unsigned long long)s.idx_off, (unsigned long long)rows, (unsigned long long)isz,
+                      (unsigned long long)local_bytes);
+        return -1;
+    }
+    // a get writes the local table: it must not write the indices the same op reads
+    if (get && local.table_rows > 0) {
+        const uint64_t t0 = local.off, t1 = local.off + (local.table_rows - 1) * local.stride + local.row_bytes;
+        const uint64_t i0 = s.idx_off, i1 = s.idx_off + rows * isz;
+        if (i0 < t1 && t0 < i1) {
+            std::snprintf(why, why_len, "%s index array [%llu, %llu) overlaps the local table [%llu, %llu) that the get writes",
+                          s.side, (unsigned long long)i0, (unsigned long long)i1, (unsigned long long)t0,
+                          (unsigned long long)t1);
             return -1;
         }
     }
-    const uint64_t isz = indexed_index_bytes(p.index_type);
-    for (const auto &s : sides) {
-        if (s.idx_off == OCM_INDEX_NONE) continue;
-        if (s.idx_off % isz) {
-            std::snprintf(why, why_len, "%s index offset %llu is not a multiple of the index size %llu", s.side,
-                          (unsigned long long)s.idx_off, (unsigned long long)isz);
+    return 0;
+}
+
+// One op against halves of local_bytes / remote_bytes. 0: fine (*moved = rows * row_bytes,
+// the nominal bytes; 0 for an empty op); -1: `why` says what is wrong. The rules are the
+// helpers above, which the converting indexed op's validator (ocm/quant_indexed.h) calls
+// as well.
+inline int indexed_check_op(const struct ocm_indexed_params &p, uint64_t local_bytes, uint64_t remote_bytes,
+                            uint64_t *moved, char *why, size_t why_len) {
+    *moved = 0;
+    if (p.rows == 0 || p.row_bytes == 0) return 0;  // does nothing, whatever else it says
+    if (indexed_check_kind(p.index_type, p.local_index_offset, p.remote_index_offset, why, why_len) != 0) return -1;
+    const IndexedSide sides[2] = {
+        {"local", p.local_offset, p.local_stride, local_bytes, p.local_rows, p.local_index_offset, p.row_bytes},
+        {"remote", p.remote_offset, p.remote_stride, remote_bytes, p.remote_rows, p.remote_index_offset, p.row_bytes}};
+    if (indexed_check_counts(p.rows, sides, why, why_len) != 0) return -1;
+    for (const auto &s : sides)
+        if (indexed_check_table(s, p.rows, why, why_len) != 0) return -1;
+    for (const auto &s : sides)
+        if (s.idx_off != OCM_INDEX_NONE &&
+            indexed_check_index_array(s, p.index_type, p.rows, local_bytes, p.op_flag == 0, sides[0], why, why_len) != 0)
             return -1;
-        }
-        if (s.idx_off > local_bytes || p.rows > (local_bytes - s.idx_off) / isz) {
-            std::snprintf(why, why_len, "%s index array [%llu, +%llu x %llu bytes) exceeds the local half's %llu bytes", s.side,
-                          (unsigned long long)s.idx_off, (unsigned long long)p.rows, (unsigned long long)isz,
-                          (unsigned long long)local_bytes);
-            return -1;
-        }
-        // a get writes the local table: it must not write the indices the same op reads
-        if (p.op_flag == 0 && p.local_rows > 0) {
-            const uint64_t t0 = p.local_offset, t1 = p.local_offset + (p.local_rows - 1) * p.local_stride + p.row_bytes;
-            const uint64_t i0 = s.idx_off, i1 = s.idx_off + p.rows * isz;
-            if (i0 < t1 && t0 < i1) {
-                std::snprintf(why, why_len, "%s index array [%llu, %llu) overlaps the local table [%llu, %llu) that the get writes",
-                              s.side, (unsigned long long)i0, (unsigned long long)i1, (unsigned long long)t0,
-                              (unsigned long long)t1);
-                return -1;
-            }
-        }
-    }
     *moved = p.rows * p.row_bytes;
     return 0;
 }

@@ -92,7 +92,7 @@ inline void list_wave_ops(const Op *ops, uint32_t n, uint64_t total_tiles, uint3
     }
 }
 
-// ---- ops with rows (strided, strided converting, indexed) ----
+// ---- ops with rows (strided, strided converting, indexed, indexed converting) ----
 // Every row of an op has tiles_per_row tiles: tile t of the op is piece t % tiles_per_row
 // of row t / tiles_per_row. A wave locates the first tile it has in an op (the only
 // divide) and counts from then on. The kernels and the stand-alone test programs run

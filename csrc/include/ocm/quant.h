@@ -29,4 +29,11 @@ hipError_t xfer_quant_launch(const XferBatchArgs &a, const XferTuning &t, hipStr
 struct XferQuantStridedArgs;
 hipError_t xfer_quant_strided_launch(const XferQuantStridedArgs &a, const XferTuning &t, hipStream_t stream);
 
+// Indexed converting lists (ocm/quant_indexed.h: the descriptor and the host plan;
+// ocm/indexed.h: the bounds rule): one launch, one record per picked row; stores as above.
+// a.skipped: a device word the kernel counts skipped rows into, copied to a.skipped_host
+// after the kernel.
+struct XferQuantIndexedArgs;
+hipError_t xfer_quant_indexed_launch(const XferQuantIndexedArgs &a, const XferTuning &t, hipStream_t stream);
+
 }  // namespace ocm

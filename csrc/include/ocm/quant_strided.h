@@ -62,19 +62,28 @@ OCM_QS_HD inline uint64_t quant_strided_tile_count(const XferQuantStridedOp &op)
     return (uint64_t)op.rows * op.tiles_per_row;
 }
 
-// Piece k of row `row`: exactly the tile (k) of the plain converting op
-// (lin_off + row * lin_stride, rem_off + row * rem_stride, row_elems). code_shift: log2 of
-// the elements a code byte of the op's format holds (quant_code_shift).
-OCM_QS_HD inline QuantTileLoc quant_strided_tile(const XferQuantStridedOp &op, uint64_t row, uint32_t k, uint32_t code_shift) {
+// THE tile rule of a row: piece k of the row of `row_elems` elements that starts at byte
+// `lrow` of the linear buffer and whose record starts at `rec` in striped coordinates,
+// exactly the tile (k) of the plain converting op (lrow, rec, row_elems). code_shift: log2
+// of the elements a code byte of the op's format holds (quant_code_shift). Which row that
+// is comes from the caller: strides (quant_strided_tile) or index arrays
+// (ocm/quant_indexed.h).
+OCM_QS_HD inline QuantTileLoc quant_row_tile(uint64_t lrow, uint64_t rec, uint32_t row_elems, uint32_t k, uint32_t code_shift) {
     const uint32_t e0 = k << kQuantTileShift;  // row_elems < 2^31
-    const uint32_t left = op.row_elems - e0;
-    const uint64_t rec = op.rem_off + row * op.rem_stride;
+    const uint32_t left = row_elems - e0;
     QuantTileLoc q;
     q.ne = left < kQuantTileElems ? left : kQuantTileElems;
-    q.lin_off = op.lin_off + row * op.lin_stride + 2ull * e0;
+    q.lin_off = lrow + 2ull * e0;
     q.codes = rec + (e0 >> code_shift);
-    q.scales = rec + (op.row_elems >> code_shift) + (e0 >> 5);
+    q.scales = rec + (row_elems >> code_shift) + (e0 >> 5);
     return q;
+}
+
+// Piece k of row `row`: exactly the tile (k) of the plain converting op
+// (lin_off + row * lin_stride, rem_off + row * rem_stride, row_elems).
+OCM_QS_HD inline QuantTileLoc quant_strided_tile(const XferQuantStridedOp &op, uint64_t row, uint32_t k, uint32_t code_shift) {
+    const uint64_t rec = op.rem_off + row * op.rem_stride;
+    return quant_row_tile(op.lin_off + row * op.lin_stride, rec, op.row_elems, k, code_shift);
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)

@@ -30,6 +30,11 @@ struct OpCounters {
     // indexed ops (ocm_copy_onesided_indexed): calls, ops, rows named, nominal bytes (rows * row_bytes),
     // rows skipped for an index outside its table (counted when their count is reported)
     uint64_t n_indexed = 0, n_indexed_ops = 0, n_indexed_rows = 0, bytes_indexed = 0, n_indexed_skipped = 0;
+    // indexed converting ops (ocm_copy_onesided_quant_indexed): calls, ops, rows named, their 16-bit source
+    // bytes and record bytes (nominal: every named row of every non-empty op); the rows they skip are
+    // counted in n_indexed_skipped, with the indexed ops'
+    uint64_t n_quant_indexed = 0, n_quant_indexed_ops = 0, n_quant_indexed_rows = 0, bytes_quant_indexed_src = 0,
+             bytes_quant_indexed_wire = 0;
 };
 
 bool trace_enabled();  // OCM_TRACE=0 disables the roctx ranges

@@ -264,8 +264,8 @@ int ocm_copy_onesided_strided(ocm_alloc_t a, const struct ocm_strided_params *op
  * table. An op with rows == 0 or row_bytes == 0 does nothing, whatever else it says.
  * flags and ordering as for ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait,
  * ocm_stream_wait/signal). Out of scope: transfer plans (ocm_plan_add takes ocm_params
- * only), the copy service, converting and accumulate variants, index-times-stride
- * (layer-major) ops and scatter-add. */
+ * only), the copy service, accumulate variants, index-times-stride (layer-major) ops and
+ * scatter-add. The converting (MX) variant is ocm_copy_onesided_quant_indexed, below. */
 #define OCM_INDEX_NONE (~0ull)
 enum ocm_index_type { OCM_INDEX_I32 = 1, OCM_INDEX_I64 = 2 };
 struct ocm_indexed_params {        /* 88 bytes */
@@ -283,6 +283,63 @@ struct ocm_indexed_params {        /* 88 bytes */
     uint32_t index_type;           /* enum ocm_index_type, both arrays alike */
 };
 int ocm_copy_onesided_indexed(ocm_alloc_t a, const struct ocm_indexed_params *ops, int n_ops, int flags);
+/* Indexed converting copies (embedding tables kept as MX records): the local side is a
+ * table of rows of row_elems 16-bit elements, the remote side a table of records, one
+ * MXFP8 or MXFP4 record per row (its codes, then its scale bytes, as for
+ * ocm_copy_onesided_quant), and which row of either table row j of the op is comes from
+ * an index array, as for ocm_copy_onesided_indexed. For j = 0 .. rows - 1, with
+ * lr = lidx[j] when the local side has an index and j when it has none, and rr likewise
+ * for the remote side: when both are in range, row j is exactly the converting op
+ * (local_offset + lr * local_stride, remote_offset + rr * remote_stride, row_elems,
+ * op_flag, dtype). By definition the call is the ocm_copy_onesided_quant list with one op
+ * per in-range row, so a plain or strided converting get can read what an indexed put
+ * wrote. Both index arrays, `rows` entries of index_type each, live in the LOCAL half at
+ * local_index_offset and remote_index_offset (OCM_INDEX_NONE: that side has no index) and
+ * are read when the transfer runs. Ops of one call and rows of one op run concurrently,
+ * puts and gets and both record formats mixed, as ONE gfx950 launch when the local half
+ * is device memory.
+ *
+ * Out-of-range indices follow the rule of ocm_copy_onesided_indexed unchanged: indices
+ * are compared as unsigned; a row with either index outside [0, table rows) of its side
+ * is skipped whole on both sides and counted once; a blocking call that skipped k > 0
+ * rows still moves every other row, then returns -1 and ocm_last_error() says
+ * "indexed ops skipped k row(s)"; after an OCM_BATCH_ASYNC call the next ocm_wait(a)
+ * returns -1 once in the same way. The count goes to the allocation's one pair of skip
+ * words, so ocm_wait has one path for both calls and the n_indexed_skipped counter counts
+ * rows skipped by either.
+ *
+ * Duplicate destination rows have no defined result, as for the indexed op; duplicates on
+ * the side being read are fine (an embedding lookup).
+ *
+ * Per op (checked at the call): dtype known; reserved == 0; row_elems % 32 == 0 and
+ * row_elems < 2^31; index_type known and at least one index; rows, local_rows and
+ * remote_rows < 2^32; local_offset and local_stride multiples of 16, remote_offset and
+ * remote_stride multiples of 32; per side with more than one table row, stride >= the
+ * row's bytes (2 * row_elems local, ocm_quant_bytes_fmt(row_elems, format) remote); per
+ * side, the table's last row ends inside its half; a side without an index has at least
+ * `rows` table rows; each index array is aligned to its element size and lies inside the
+ * local half; for a get, no index array overlaps the op's local table. An op with
+ * rows == 0 or row_elems == 0 does nothing. flags and ordering as for
+ * ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait, ocm_stream_wait/signal). Out of
+ * scope: transfer plans (ocm_plan_add takes ocm_params only), the copy service,
+ * index-times-stride (layer-major) ops and scatter-add. */
+struct ocm_quant_indexed_params {   /* 96 bytes */
+    uint64_t local_offset;          /* first element of local table row 0 (bytes), multiple of 16 */
+    uint64_t remote_offset;         /* first byte of remote table row 0's record, multiple of 32 */
+    uint64_t row_elems;             /* 16-bit elements per row: multiple of 32, < 2^31; 0 = empty op */
+    uint64_t rows;                  /* rows moved = entries of each index array, < 2^32; 0 = empty op */
+    uint64_t local_stride;          /* multiple of 16 */
+    uint64_t remote_stride;         /* multiple of 32 */
+    uint64_t local_index_offset;    /* in the LOCAL half, or OCM_INDEX_NONE */
+    uint64_t remote_index_offset;
+    uint64_t local_rows;            /* rows each table has, < 2^32 */
+    uint64_t remote_rows;
+    int32_t  op_flag;               /* 1 = put (encode), 0 = get (decode) */
+    uint32_t index_type;            /* enum ocm_index_type */
+    uint32_t dtype;                 /* enum ocm_quant_dtype | enum ocm_quant_format */
+    uint32_t reserved;              /* must be 0 */
+};
+int ocm_copy_onesided_quant_indexed(ocm_alloc_t a, const struct ocm_quant_indexed_params *ops, int n_ops, int flags);
 /* One-sided accumulate (the counterpart of MPI_Accumulate): the remote half holds fp32
  * accumulators, the local half elements of `dtype`, and for every element i of every op
  *     remote_f32[i] = remote_f32[i] + scale * widen(local[i]).

@@ -1,4 +1,5 @@
-// The tile bodies of the converting kernels (xfer_quant.hip, xfer_quant_strided.hip):
+// The tile bodies of the converting kernels (xfer_quant.hip, xfer_quant_strided.hip,
+// xfer_quant_indexed.hip):
 // one wave encodes (put_tile) or decodes (get_tile) one wave-tile of at most
 // kQuantTileElems elements, given where its elements, its codes and its scale bytes
 // lie. How a kernel finds those three places is its own rule (ocm/quant.h: a tile of a

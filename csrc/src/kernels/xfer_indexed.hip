@@ -19,6 +19,7 @@
 // data of the local half.
 #include <hip/hip_runtime.h>
 
+#include "indexed_row.h"
 #include "ocm/indexed.h"
 #include "ocm/xfer.h"
 #include "xfer_copy.h"
@@ -29,33 +30,14 @@ namespace ocm {
 namespace {
 
 // What a wave keeps of its op across the copy loops, in scalar registers (uniform32 /
-// uniform64, xfer_copy.h). The fields that only entering a row needs (enter_row) are
-// read from the descriptor there, in the kernel arguments or in L2, beside the index
-// loads they would wait for anyway: kept live as well, they cost register spills.
+// uniform64, xfer_copy.h). The fields that only entering a row needs (enter_row,
+// indexed_row.h) are read from the descriptor there, in the kernel arguments or in L2,
+// beside the index loads they would wait for anyway: kept live as well, they cost
+// register spills.
 struct OpInLoop {
     uint64_t row_bytes, tiles_per_row;
     uint32_t put;
 };
-
-// The table row that entry j of the index array at `idx_off` of the local half picks
-// (no array: row j itself), widened for indexed_in_range. One value per wave.
-__device__ __forceinline__ uint64_t row_of(const char *lin, uint64_t idx_off, uint32_t index_type, uint64_t j) {
-    if (idx_off == OCM_INDEX_NONE) return j;
-    if (index_type == OCM_INDEX_I64) return uniform64(*reinterpret_cast<const uint64_t *>(lin + idx_off + (j << 3)));
-    return indexed_widen32(uniform32(*reinterpret_cast<const uint32_t *>(lin + idx_off + (j << 2))));
-}
-
-// The wave enters row j of op *d: both indices, the bounds rule, and where the row starts
-// on either side. False: the row is skipped (*lrow / *rrow are then not to be used).
-__device__ __forceinline__ bool enter_row(const char *lin, const XferIndexedOp *d, uint64_t j, uint64_t *lrow, uint64_t *rrow) {
-    const uint32_t type = uniform32(d->index_type);
-    const uint64_t lr = row_of(lin, uniform64(d->lin_idx_off), type, j);
-    const uint64_t rr = row_of(lin, uniform64(d->rem_idx_off), type, j);
-    // in range, and the table fits its half (indexed_check_op): neither product can overflow
-    *lrow = uniform64(d->lin_off) + lr * uniform64(d->lin_stride);
-    *rrow = uniform64(d->rem_off) + rr * uniform64(d->rem_stride);
-    return indexed_in_range(lr, uniform32(d->lin_rows)) && indexed_in_range(rr, uniform32(d->rem_rows));
-}
 
 template <bool NT, bool HOST>
 __global__ __launch_bounds__(kThreads) void xfer_indexed_kernel(XferIndexedArgs a) {

@@ -31,9 +31,11 @@ static int check_indexed_ops(lib_alloc *a, const struct ocm_indexed_params *ops,
     return 0;
 }
 
+namespace ocmlib {
+
 // The allocation's skip words, made on first use (the device word zeroed on `st`, which
 // every later op of the allocation is ordered after).
-static int skip_words(lib_alloc *a, hipStream_t st) {
+int skip_words(lib_alloc *a, hipStream_t st) {
     if (a->skip_dev) return 0;
     State &s = S();
     void *dev = nullptr, *host = nullptr;
@@ -52,8 +54,6 @@ static int skip_words(lib_alloc *a, hipStream_t st) {
     return 0;
 }
 
-namespace ocmlib {
-
 int indexed_take_skips(lib_alloc *a) {
     uint64_t k = a->skip_host_path;
     a->skip_host_path = 0;
@@ -62,6 +62,10 @@ int indexed_take_skips(lib_alloc *a) {
         k += now - a->skip_seen;
         a->skip_seen = now;
     }
+    return indexed_fail_skips(k);
+}
+
+int indexed_fail_skips(uint64_t k) {
     if (k == 0) return 0;
     S().ctr.n_indexed_skipped += k;
     OCM_FAIL(-1, "indexed ops skipped %llu row(s): index outside its table", (unsigned long long)k);
@@ -136,8 +140,7 @@ static int indexed_impl(ocm_alloc_t a, const struct ocm_indexed_params *ops, int
             a->skip_host_path += skipped;
             return 0;
         }
-        s.ctr.n_indexed_skipped += skipped;
-        OCM_FAIL(-1, "indexed ops skipped %llu row(s): index outside its table", (unsigned long long)skipped);
+        return indexed_fail_skips(skipped);
     }
     DeviceGuard guard(s.device);
     std::vector<XferIndexedOp> v((size_t)n_ops);
@@ -154,10 +157,8 @@ static int indexed_impl(ocm_alloc_t a, const struct ocm_indexed_params *ops, int
     *ran = true;
     if (async) return 0;
     const uint64_t k = __atomic_load_n(a->skip_host, __ATOMIC_ACQUIRE) - base;
-    if (k == 0) return 0;
     a->skip_seen += k;
-    s.ctr.n_indexed_skipped += k;
-    OCM_FAIL(-1, "indexed ops skipped %llu row(s): index outside its table", (unsigned long long)k);
+    return indexed_fail_skips(k);
 }
 
 extern "C" {

@@ -9,6 +9,7 @@
 // quant_strided.cpp  strided converting ops (ocm_copy_onesided_quant_strided: one MXFP8 record per row)
 // strided.cpp  strided one-sided ops (ocm_copy_onesided_strided: rows, one stride per side)
 // indexed.cpp  indexed one-sided ops (ocm_copy_onesided_indexed: rows picked by index arrays in the local half)
+// quant_indexed.cpp  indexed converting ops (ocm_copy_onesided_quant_indexed: one MX record per row picked by index arrays)
 // acc.cpp      one-sided accumulate (ocm_copy_onesided_accumulate: remote fp32 += scale * local)
 // libocm.cpp   the C ABI (oncillamem.h)
 // config.cpp   the environment's knobs, parsed once per ocm_init into State::cfg
@@ -499,10 +500,16 @@ void before_launch();
 
 // ---- descriptor lists (batches and their kin): lists.h
 
-// ---- indexed ops (indexed.cpp)
-// Rows that `a`'s completed async indexed ops skipped and no call has reported yet: 0 when
-// there are none, else -1 with the error set, once (ocm_wait).
+// ---- indexed ops (indexed.cpp), and the indexed converting ops that share their skip count (quant_indexed.cpp)
+// The allocation's skip words (skip_dev, skip_host), made on first use: the device word
+// zeroed on `st`, which every later op of the allocation is ordered after.
+int skip_words(lib_alloc *a, hipStream_t st);
+// Rows that `a`'s completed async indexed ops, of either call, skipped and no call has
+// reported yet: 0 when there are none, else -1 with the error set, once (ocm_wait).
 int indexed_take_skips(lib_alloc *a);
+// Reports k rows as skipped: 0 when k is 0, else counts them (n_indexed_skipped) and
+// returns -1 with the error "indexed ops skipped k row(s)" set.
+int indexed_fail_skips(uint64_t k);
 // Frees the allocation's skip words (ocm_free).
 void indexed_release(lib_alloc *a);
 

@@ -50,6 +50,17 @@ void ocm_x_indexed_counters(uint64_t out[5]) {
     out[4] = c.n_indexed_skipped;
 }
 
+// The indexed converting counters, likewise: calls, ops, rows named, 16-bit source bytes, record
+// bytes (rows skipped are in ocm_x_indexed_counters' n_indexed_skipped, with the indexed ops').
+void ocm_x_quant_indexed_counters(uint64_t out[5]) {
+    const OpCounters &c = S().ctr;
+    out[0] = c.n_quant_indexed;
+    out[1] = c.n_quant_indexed_ops;
+    out[2] = c.n_quant_indexed_rows;
+    out[3] = c.bytes_quant_indexed_src;
+    out[4] = c.bytes_quant_indexed_wire;
+}
+
 // Raw 64-byte handle of extent i (tests: the network tier's capability checks).
 int ocm_x_extent_handle(ocm_alloc_t a, int i, uint8_t *out) {
     if (!a || !out || i < 0 || (size_t)i >= a->ext.size()) return -1;

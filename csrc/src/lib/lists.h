@@ -1,6 +1,7 @@
 // What the kinds of descriptor list share on the host (batches in batch.cpp, converting
 // ops in quant.cpp, strided ops in strided.cpp, strided converting ops in
-// quant_strided.cpp, indexed ops in indexed.cpp, accumulates in acc.cpp): how a
+// quant_strided.cpp, indexed ops in indexed.cpp, indexed converting ops in
+// quant_indexed.cpp, accumulates in acc.cpp): how a
 // call is entered and accounted, how launch arguments are filled from the pair and the
 // plan (ocm/list.h), how a large list's descriptors and wave table are packed for the
 // device, and the upload, launch and completion of one list (run_list). A kind brings
@@ -141,7 +142,8 @@ int run_list(lib_alloc *a, Args &args, const std::vector<Op> &v,
 // The host path of converting ops (quant.cpp): a CPU app, a host local half, the network
 // tier. Encodes or decodes the plain ops `next` yields (false: no more), in order, on this
 // thread and moves each record with xfer(). Converting lists yield their ops, strided
-// converting lists (quant_strided.cpp) one op per row.
+// converting lists (quant_strided.cpp) one op per row, indexed converting lists
+// (quant_indexed.cpp) one op per row whose indices are in range.
 int quant_host(lib_alloc *a, const std::function<bool(ocm_quant_params *)> &next);
 
 // Copy absolute device ranges (op.lin_off = address) into dst's remote half, one launch.

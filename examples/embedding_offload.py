@@ -9,6 +9,12 @@ where they are (on the GPU with --gpu), and check them against torch.index_selec
 4. scatter new rows into the table and read them back; 5. an id outside the table is
 skipped, counted and reported.
 
+    python examples/embedding_offload.py --compress mxfp8     # or mxfp4; with or without --gpu
+
+keeps the table as MX records, one per row (RemoteEmbedding(compress=...)): each lookup ONE indexed
+converting get, checked against the oracle round trip (decode of encode) of torch.index_select, and
+the table's remote bytes printed against the uncompressed size.
+
     python examples/embedding_offload.py --gpu 0 --train
 
 trains a second, fp32 table where it lives (oncilla_amd.models.RemoteEmbeddingAdam): a few steps of
@@ -26,6 +32,8 @@ import torch  # noqa: E402
 
 from oncilla_amd import api  # noqa: E402
 from oncilla_amd.models import RemoteEmbedding, RemoteEmbeddingAdam  # noqa: E402
+from oncilla_amd.ops import (mx4_decode_reference, mx4_encode_reference, mx8_decode_reference,  # noqa: E402
+                             mx8_encode_reference)
 from oncilla_amd.parallel import Mesh  # noqa: E402
 
 
@@ -75,11 +83,21 @@ def train(c, kind, dev, rows, dim, g, steps=5, batch=1024):
     return True
 
 
+def roundtrip(rows, fmt):
+    """What a compressed table gives back for `rows`: the oracle decode of their oracle encode (no format: the rows)."""
+    if fmt is None:
+        return rows
+    enc, dec = {"mxfp8": (mx8_encode_reference, mx8_decode_reference), "mxfp4": (mx4_encode_reference, mx4_decode_reference)}[fmt]
+    codes, scales = enc(rows.reshape(-1))
+    return dec(codes, scales, rows.dtype).view(rows.shape)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--rows", type=int, default=20000)
     ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--compress", choices=["mxfp8", "mxfp4"], default=None, help="keep the table as MX records, one per row")
     ap.add_argument("--train", action="store_true", help="also train a table in place with the fused row-sparse Adam")
     args = ap.parse_args()
     if args.gpu is None:
@@ -90,9 +108,11 @@ def main():
     g = torch.Generator().manual_seed(0)
     with Mesh(3, gpus=gpus, policy="stripe") as mesh:
         with api.Client(daemon_rank=0, gpu=args.gpu, ns=mesh.ns) as c:
-            emb = RemoteEmbedding(c, args.rows, args.dim, torch.float16, max_ids=2048, kind=kind, stripe_unit=1 << 16)
+            emb = RemoteEmbedding(c, args.rows, args.dim, torch.float16, max_ids=2048, kind=kind, stripe_unit=1 << 16,
+                                  compress=args.compress)
             table = torch.randn((args.rows, args.dim), generator=g).to(torch.float16)
             emb.load(table.to(dev))
+            table = roundtrip(table, args.compress)  # what the remote half now holds, decoded
             for dtype in (torch.int64, torch.int32):
                 ids = torch.randint(0, args.rows, (2048,), generator=g).to(dtype)
                 ids[100:110] = ids[0]  # repeats are fine on the side being read
@@ -103,6 +123,7 @@ def main():
             ids = torch.randperm(args.rows, generator=g)[:512]
             new = torch.randn((512, args.dim), generator=g).to(torch.float16)
             emb.update(ids.to(dev), new.to(dev))
+            new = roundtrip(new, args.compress)
             table[ids] = new
             assert torch.equal(emb.lookup(ids.to(dev), async_=False).cpu(), new)
             # an id outside the table moves nothing and is reported
@@ -113,8 +134,15 @@ def main():
             except IndexError as e:
                 print("out of range:", e)
             assert torch.equal(emb.out[[0, 2]].cpu(), table[[3, 5]])
-            print(f"{args.rows} x {args.dim} fp16 table in remote memory: lookups equal index_select;",
-                  {k: v for k, v in api.indexed_counters().items()})
+            if args.compress:
+                plain = args.rows * emb.row_bytes
+                print(f"{args.rows} x {args.dim} fp16 table in remote memory as {args.compress} records: lookups equal the "
+                      f"{args.compress} round trip of index_select; remote bytes {emb.remote_bytes} against {plain} "
+                      f"uncompressed ({emb.remote_bytes / plain:.3f});", api.quant_indexed_counters(),
+                      {"n_indexed_skipped": api.indexed_counters()["n_indexed_skipped"]})
+            else:
+                print(f"{args.rows} x {args.dim} fp16 table in remote memory: lookups equal index_select;",
+                      {k: v for k, v in api.indexed_counters().items()})
             emb.close()
             if args.train:
                 train(c, kind, dev, args.rows, args.dim, g)

@@ -119,6 +119,30 @@ class OcmIndexedParams(ctypes.Structure):
 assert ctypes.sizeof(OcmIndexedParams) == 88
 
 
+class OcmQuantIndexedParams(ctypes.Structure):
+    """struct ocm_quant_indexed_params (96 bytes)."""
+
+    _fields_ = [
+        ("local_offset", ctypes.c_uint64),
+        ("remote_offset", ctypes.c_uint64),
+        ("row_elems", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("local_stride", ctypes.c_uint64),
+        ("remote_stride", ctypes.c_uint64),
+        ("local_index_offset", ctypes.c_uint64),
+        ("remote_index_offset", ctypes.c_uint64),
+        ("local_rows", ctypes.c_uint64),
+        ("remote_rows", ctypes.c_uint64),
+        ("op_flag", ctypes.c_int32),
+        ("index_type", ctypes.c_uint32),
+        ("dtype", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(OcmQuantIndexedParams) == 96
+
+
 class OcmAdamRows(ctypes.Structure):
     """struct ocm_adam_rows (csrc/include/ocm/adam_rows.h): the descriptor of one row-sparse Adam step."""
     _fields_ = [
@@ -263,6 +287,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_copy_onesided_quant_strided": (i32, [vp, ctypes.POINTER(OcmQuantStridedParams), i32, i32]),
             "ocm_copy_onesided_strided": (i32, [vp, ctypes.POINTER(OcmStridedParams), i32, i32]),
             "ocm_copy_onesided_indexed": (i32, [vp, ctypes.POINTER(OcmIndexedParams), i32, i32]),
+            "ocm_copy_onesided_quant_indexed": (i32, [vp, ctypes.POINTER(OcmQuantIndexedParams), i32, i32]),
             "ocm_copy_onesided_accumulate": (i32, [vp, ctypes.POINTER(OcmAccParams), i32, i32]),
             "ocm_stream_wait": (i32, [vp, vp]),
             "ocm_plan_create": (vp, []),
@@ -290,6 +315,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_x_acc_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_quant_strided_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_indexed_counters": (None, [ctypes.POINTER(u64)]),
+            "ocm_x_quant_indexed_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_stats": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_health": (None, [ctypes.POINTER(u64)]),
             "ocm_x_tick_stats": (ctypes.c_int, [ctypes.POINTER(u64)]),
@@ -386,6 +412,8 @@ OCM_INDEX_NONE = (1 << 64) - 1  # an indexed op's side without an index array
 OCM_INDEX_I32 = 1
 OCM_INDEX_I64 = 2
 INDEXED_COUNTER_KEYS = ["n_indexed", "n_indexed_ops", "n_indexed_rows", "bytes_indexed", "n_indexed_skipped"]
+QUANT_INDEXED_COUNTER_KEYS = ["n_quant_indexed", "n_quant_indexed_ops", "n_quant_indexed_rows", "bytes_quant_indexed_src",
+                              "bytes_quant_indexed_wire"]
 
 
 class Plan:
@@ -593,6 +621,45 @@ def indexed_ops(ops, index_type=OCM_INDEX_I64) -> BatchOps:
     b.keep = rec
     b.indexed = True
     return b
+
+
+def quant_indexed_ops(ops, dtype, index_type=OCM_INDEX_I64, format="mxfp8") -> BatchOps:
+    """Descriptor list for Allocation.quant_indexed_batch from an (n, 11) integer array (or rows)
+    [op_flag, local_offset, remote_offset, row_elems, rows, local_stride, remote_stride,
+    local_index_offset, remote_index_offset, local_rows, remote_rows]: the columns of
+    :func:`indexed_ops` with row_elems in place of row_bytes, every op with `dtype`, built once (no
+    per-op Python objects). A side without an index has OCM_INDEX_NONE (or -1) as its index offset.
+    index_type: the element type of every index array (see :func:`index_type_of`). format: "mxfp8"
+    or "mxfp4" for every op, or a sequence with one of them per op."""
+    import numpy as np
+
+    if isinstance(ops, np.ndarray) and ops.dtype.kind in "iu":
+        a = ops.astype(np.uint64).reshape(-1, 11)  # -1 wraps to OCM_INDEX_NONE
+    else:  # Python integers: OCM_INDEX_NONE fits no int64
+        flat = np.array(ops, dtype=object).reshape(-1)
+        a = np.array([int(v) & OCM_INDEX_NONE for v in flat], dtype=np.uint64).reshape(-1, 11)
+    n = int(a.shape[0])
+    rec = np.zeros(max(1, n), dtype=np.dtype([("lo", "<u8"), ("ro", "<u8"), ("re", "<u8"), ("rows", "<u8"), ("ls", "<u8"),
+                                              ("rs", "<u8"), ("li", "<u8"), ("ri", "<u8"), ("lr", "<u8"), ("rr", "<u8"),
+                                              ("flag", "<i4"), ("it", "<u4"), ("dt", "<u4"), ("rsv", "<u4")]))
+    if n:
+        for col, name in enumerate(("flag", "lo", "ro", "re", "rows", "ls", "rs", "li", "ri", "lr", "rr")):
+            rec[name][:n] = a[:, col]
+        rec["it"][:n] = index_type_of(index_type)
+        rec["dt"][:n] = quant_dtype(dtype) | _quant_formats(format)
+    b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmQuantIndexedParams)), n)
+    b.keep = rec
+    b.quant_indexed = True
+    return b
+
+
+def quant_indexed_counters() -> dict:
+    """This process's indexed converting counters (ocm_x_quant_indexed_counters): calls, ops, rows
+    named, their 16-bit source bytes and record bytes (nominal: every named row of every non-empty
+    op). The rows they skip are counted in indexed_counters()["n_indexed_skipped"]."""
+    out = (ctypes.c_uint64 * len(QUANT_INDEXED_COUNTER_KEYS))()
+    load().ocm_x_quant_indexed_counters(out)
+    return dict(zip(QUANT_INDEXED_COUNTER_KEYS, [int(v) for v in out]))
 
 
 def indexed_counters() -> dict:
@@ -1123,6 +1190,22 @@ class Allocation:
             raise TypeError("indexed_batch takes an indexed_ops list, not a batch_ops, quant_ops, strided_ops or acc_ops one")
         if self._c.lib.ocm_copy_onesided_indexed(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_indexed: " + last_error())
+
+    def quant_indexed_batch(self, ops, dtype=None, index_type=OCM_INDEX_I64, async_: bool = False, format="mxfp8") -> None:
+        """Indexed converting ops in one launch (ocm_copy_onesided_quant_indexed): row j of an op is
+        the converting op between local table row lidx[j] (row_elems 16-bit elements) and remote
+        table row ridx[j] (its MXFP8 or MXFP4 record), the index arrays in the LOCAL half. Rows with an
+        index outside its table are skipped and counted, as for indexed_batch: the call (or, async,
+        the next wait()) then raises OcmError naming the count, after moving every other row. ops:
+        rows for :func:`quant_indexed_ops` with `dtype`, `index_type` and `format`, or a prepared
+        quant_indexed_ops list."""
+        arr = ops if isinstance(ops, BatchOps) else quant_indexed_ops(ops, dtype, index_type, format)
+        if not getattr(arr, "quant_indexed", False):
+            raise TypeError("quant_indexed_batch takes a quant_indexed_ops list, not a batch_ops, quant_ops, "
+                            "quant_strided_ops, strided_ops, indexed_ops or acc_ops one")
+        if self._c.lib.ocm_copy_onesided_quant_indexed(self.handle, arr.array, arr.n,
+                                                       OCM_BATCH_ASYNC if async_ else 0) != 0:
+            raise OcmError("ocm_copy_onesided_quant_indexed: " + last_error())
 
     def strided_batch(self, ops, async_: bool = False) -> None:
         """Strided one-sided ops in one launch (ocm_copy_onesided_strided): row r of an op moves

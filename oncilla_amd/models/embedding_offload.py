@@ -11,6 +11,14 @@ Streams: a lookup waits for the work already queued on torch's current stream (t
 kernel that produced the ids) and, when async, makes that stream wait for the copy, so
 the rows can be consumed there without a host sync.
 
+``compress="mxfp8"`` or ``"mxfp4"`` keeps the table as MX records in the remote half, one
+record per row (its codes, then its scale bytes: the layout of ocm_copy_onesided_quant) at a
+stride of the record bytes rounded up to 32: 33/64 or 17/64 of the bytes cross the link and,
+but for that padding, lie in the pool. ``load`` is then the strided converting put, a lookup ONE
+indexed converting get (ocm_copy_onesided_quant_indexed) and ``update`` the indexed converting
+put; a lookup returns the decode of the encode of the rows that were loaded, which is not the
+rows themselves. Ids, streams and out-of-range ids are as without it.
+
 Ids outside [0, num_rows) move nothing: their output rows keep what they held, they are
 counted, and IndexError names the count, at once for a blocking lookup and at ``wait()``
 for an async one.
@@ -29,24 +37,38 @@ def _index_error(e: api.OcmError):
 
 
 class RemoteEmbedding:
-    """num_rows x dim table of `dtype` in a remote half; lookups of up to max_ids ids."""
+    """num_rows x dim table of `dtype` in a remote half; lookups of up to max_ids ids. compress:
+    None, or "mxfp8" / "mxfp4" for a table of float16 or bfloat16 rows with dim % 32 == 0 kept as
+    one MX record per row. record_stride: bytes from one row to the next in the remote half;
+    remote_bytes: the bytes the table takes there."""
 
     def __init__(self, client: api.Client, num_rows: int, dim: int, dtype=None, max_ids: int = 4096,
                  kind: int = api.OCM_REMOTE_GPU, flags: int = api.OCM_ALLOC_STRIPE, stripe_unit: int = 0,
-                 remote_rank: int = -1):
+                 remote_rank: int = -1, compress=None):
         import torch
 
         self.dtype = dtype or torch.float16
+        self.compress = compress
         self.client = client
         self._place = dict(kind=kind, flags=flags, stripe_unit=stripe_unit, remote_rank=remote_rank)
         self.num_rows, self.dim, self.max_ids = int(num_rows), int(dim), int(max_ids)
         if self.num_rows < 1 or self.dim < 1 or self.max_ids < 1:
             raise ValueError("num_rows, dim and max_ids must be positive")
         self.row_bytes = self.dim * torch.empty((), dtype=self.dtype).element_size()
+        # bytes from one table row to the next in the remote half, and the bytes the table takes there
+        self.record_stride = self.row_bytes
+        if compress is not None:
+            api.quant_format(compress)  # ValueError for anything but "mxfp8" / "mxfp4"
+            if self.dtype not in (torch.float16, torch.bfloat16):
+                raise ValueError(f"a compressed table holds float16 or bfloat16 rows, not {self.dtype}")
+            if self.dim % 32 != 0:
+                raise ValueError(f"a compressed table needs dim % 32 == 0 (one scale per 32 elements), not dim {self.dim}")
+            self.record_stride = (api.quant_bytes(self.dim, compress) + 31) // 32 * 32
+        self.remote_bytes = self.num_rows * self.record_stride
         out_bytes = self.max_ids * self.row_bytes
         self._ids_off = (out_bytes + 15) // 16 * 16  # int64 ids, or int32 in the same region
         self.alloc = client.alloc(kind, local_bytes=self._ids_off + 8 * self.max_ids,
-                                  remote_bytes=self.num_rows * self.row_bytes, remote_rank=remote_rank, flags=flags,
+                                  remote_bytes=self.remote_bytes, remote_rank=remote_rank, flags=flags,
                                   stripe_unit=stripe_unit)
         raw = self.alloc.local_tensor(torch.uint8)
         # zero-copy views of the local half: the rows a lookup returns, and where its ids go
@@ -62,7 +84,11 @@ class RemoteEmbedding:
             n = min(self.max_ids, self.num_rows - r)
             self.out[:n].copy_(weight[r:r + n])
             self.alloc.stream_wait()
-            self.alloc.put(0, r * self.row_bytes, n * self.row_bytes)  # blocking: the region is free again
+            if self.compress is None:
+                self.alloc.put(0, r * self.row_bytes, n * self.row_bytes)  # blocking: the region is free again
+            else:  # one record per row, blocking likewise
+                self.alloc.quant_strided_batch([[1, 0, r * self.record_stride, self.dim, n, self.row_bytes, self.record_stride]],
+                                               self.dtype, format=self.compress)
 
     def _stage_ids(self, ids):
         import torch
@@ -78,10 +104,15 @@ class RemoteEmbedding:
 
     def _run(self, put: bool, k: int, itype: int, async_: bool) -> None:
         rb = self.row_bytes
-        op = [[1 if put else 0, 0, 0, rb, k, rb, rb, api.OCM_INDEX_NONE, self._ids_off, self.max_ids, self.num_rows]]
+        # row_bytes, or for a compressed table row_elems, in column 3
+        op = [[1 if put else 0, 0, 0, rb if self.compress is None else self.dim, k, rb, self.record_stride, api.OCM_INDEX_NONE,
+               self._ids_off, self.max_ids, self.num_rows]]
         self.alloc.stream_wait()  # after the id copy, and the kernel that produced the ids
         try:
-            self.alloc.indexed_batch(api.indexed_ops(op, itype), async_=async_)
+            if self.compress is None:
+                self.alloc.indexed_batch(api.indexed_ops(op, itype), async_=async_)
+            else:
+                self.alloc.quant_indexed_batch(api.quant_indexed_ops(op, self.dtype, itype, self.compress), async_=async_)
         except api.OcmError as e:
             raise _index_error(e) from None
         if async_:
@@ -133,6 +164,9 @@ class RemoteEmbeddingAdam:
                  weight_decay: float = 0.0):
         import torch
 
+        if getattr(emb, "compress", None) is not None:
+            raise TypeError(f"RemoteEmbeddingAdam does not serve a compressed ({emb.compress}) table: "
+                            "training a quantized table is not defined here")
         if emb.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"RemoteEmbeddingAdam serves float32 and bfloat16 tables, not {emb.dtype} "
                             "(RemoteEmbedding's default dtype is float16: pass dtype=torch.float32 or torch.bfloat16)")

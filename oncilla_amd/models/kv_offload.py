@@ -31,6 +31,11 @@ list one launch, and every layer comes back rounded to the format on its own.
 records (E2M1 codes, two to a byte, ``oncilla_amd.ops.mx4_encode_reference``): 17/64 of
 the bytes, so a pool of the same size holds 1.94 times the blocks of an MXFP8 one.
 
+Indexed swaps (``indexed_ids``) cover the plain cache only: combined with ``compress`` they
+raise ValueError. The library has the call they would take, indexed rows of MX records
+(ocm_copy_onesided_quant_indexed, which RemoteEmbedding uses); compressed indexed KV swaps
+are a later change.
+
 Streams: swap_out waits for work already queued on torch's current stream (the
 kernels that wrote the cache). After an async swap_in, that stream waits for the
 copies, so later attention kernels see the blocks without a host sync.
