@@ -18,11 +18,12 @@
 // written them just before, and what orders the transfer after that kernel is
 // ocm_stream_wait, as for the rows themselves.
 //
-// Out of scope: transfer plans and hipGraph capture, the copy service, accumulate
+// Out of scope: transfer plans and hipGraph capture, the copy service, put-side accumulate
 // variants, index-times-stride (layer-major) ops, a defined result for duplicate
 // destination rows, and scatter-add. The converting (MX) variant is a call of its own,
-// ocm_copy_onesided_quant_indexed (ocm/quant_indexed.h), which shares the bounds rule, the
-// validator's helpers and the skip count of this one.
+// ocm_copy_onesided_quant_indexed (ocm/quant_indexed.h), and so is the gather-side
+// accumulate, the pooled lookup ocm_copy_onesided_bag (ocm/bag.h); both share the bounds
+// rule, the validator's helpers and the skip count of this one.
 //
 // This header is what the kernel (xfer_indexed.hip), the host side (indexed.cpp) and the
 // stand-alone test program (ocm_indexed_tests.cpp) share; it needs no HIP.

@@ -35,6 +35,9 @@ struct OpCounters {
     // counted in n_indexed_skipped, with the indexed ops'
     uint64_t n_quant_indexed = 0, n_quant_indexed_ops = 0, n_quant_indexed_rows = 0, bytes_quant_indexed_src = 0,
              bytes_quant_indexed_wire = 0;
+    // pooled lookups (ocm_copy_onesided_bag): calls, ops, bags and ids named, nominal bytes read
+    // (ids * row bytes); the entries they skip are counted in n_indexed_skipped, with the indexed ops'
+    uint64_t n_bag = 0, n_bag_ops = 0, n_bag_bags = 0, n_bag_ids = 0, bytes_bag = 0;
 };
 
 bool trace_enabled();  // OCM_TRACE=0 disables the roctx ranges

@@ -143,6 +143,12 @@ hipError_t xfer_strided_launch(const XferStridedArgs &a, const XferTuning &t, hi
 struct XferIndexedArgs;
 hipError_t xfer_indexed_launch(const XferIndexedArgs &a, const XferTuning &t, hipStream_t stream);
 
+// Pooled lookups (ocm/bag.h: the descriptors, the rule and the host plan): one launch;
+// a.grid from xfer_batch_grid, a.wave_op from list_wave_ops, a.skipped the device word the
+// indexed kernels count into.
+struct XferBagArgs;
+hipError_t xfer_bag_launch(const XferBagArgs &a, const XferTuning &t, hipStream_t stream);
+
 // Accumulate lists (ocm/acc.h: the element rule, the tile count and the descriptor
 // packing): one launch; a.grid from xfer_batch_grid, a.wave_op from list_wave_ops.
 // Stores are nontemporal (t.nontemporal), plain into a pool wholly in the pinned host tier.

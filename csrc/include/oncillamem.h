@@ -264,8 +264,9 @@ int ocm_copy_onesided_strided(ocm_alloc_t a, const struct ocm_strided_params *op
  * table. An op with rows == 0 or row_bytes == 0 does nothing, whatever else it says.
  * flags and ordering as for ocm_copy_onesided_batch (OCM_BATCH_ASYNC, ocm_wait,
  * ocm_stream_wait/signal). Out of scope: transfer plans (ocm_plan_add takes ocm_params
- * only), the copy service, accumulate variants, index-times-stride (layer-major) ops and
- * scatter-add. The converting (MX) variant is ocm_copy_onesided_quant_indexed, below. */
+ * only), the copy service, put-side accumulate variants, index-times-stride (layer-major)
+ * ops and scatter-add. The converting (MX) variant is ocm_copy_onesided_quant_indexed, the
+ * gather that sums the rows of a bag ocm_copy_onesided_bag, both below. */
 #define OCM_INDEX_NONE (~0ull)
 enum ocm_index_type { OCM_INDEX_I32 = 1, OCM_INDEX_I64 = 2 };
 struct ocm_indexed_params {        /* 88 bytes */
@@ -340,6 +341,59 @@ struct ocm_quant_indexed_params {   /* 96 bytes */
     uint32_t reserved;              /* must be 0 */
 };
 int ocm_copy_onesided_quant_indexed(ocm_alloc_t a, const struct ocm_quant_indexed_params *ops, int n_ops, int flags);
+/* Pooled embedding lookup (nn.EmbeddingBag's forward; a get only): the remote half holds a
+ * table of remote_rows rows of row_elems elements of `dtype` (enum ocm_acc_dtype, below),
+ * the local half an array of `ids` row numbers cut into `bags` bags by an offsets array of
+ * bags + 1 entries (include-last-offset form), optionally one fp32 weight per id, and an
+ * output table of `bags` rows of the same elements, written in bag order. All three arrays
+ * live in the LOCAL half and are read when the transfer runs, as the index arrays of
+ * ocm_copy_onesided_indexed are. The result is defined bit for bit (ocm/bag.h). For bag b:
+ *   lo = min(off[b], ids), hi = min(off[b + 1], ids), compared as unsigned after int32
+ *   values are sign-extended; hi < lo is an empty bag;
+ *   acc[e] = +0, then for j = lo .. hi - 1 in that order
+ *       acc[e] = fl32(acc[e] + fl32(w[j] * widen(table[id[j]][e])))
+ *   (two roundings, never an fma; without weights fl32(acc[e] + widen(x))) when id[j] is
+ *   inside [0, remote_rows) compared as unsigned; otherwise entry j adds nothing;
+ *   OCM_BAG_MEAN: acc[e] = fl32(acc[e] / (float)(hi - lo)) when hi > lo;
+ *   out[b][e] = acc[e] narrowed to dtype, round to nearest even. An empty bag writes zeros.
+ * Duplicate ids in a bag add twice. The remote half is only read. Ops of one call and bags
+ * of one op run concurrently, as ONE gfx950 launch when the local half is device memory.
+ *
+ * Out-of-range ids are counted once per entry and reported exactly as the indexed ops'
+ * skipped rows are: the call still writes every bag, then returns -1 and ocm_last_error()
+ * says "indexed ops skipped k row(s)"; after an OCM_BATCH_ASYNC call the next ocm_wait(a)
+ * returns -1 once in the same way. The count goes to the allocation's one pair of skip
+ * words and to the n_indexed_skipped counter. A mean divides by hi - lo, skipped entries
+ * included.
+ *
+ * Per op (checked at the call): index_type, dtype and mode known, reserved == 0; no weights
+ * with OCM_BAG_MEAN; row_elems * size(dtype) a positive multiple of 16 below 2^32; bags, ids
+ * and remote_rows < 2^32; offsets and strides of both tables multiples of 16; per table with
+ * more than one row, stride >= the row's bytes, and the table's last row ends inside its
+ * half; each array is aligned to its element size, lies inside the local half and does not
+ * overlap the output table. An op with bags == 0 does nothing; one with ids == 0 writes
+ * zeros to every bag. flags and ordering as for ocm_copy_onesided_batch (OCM_BATCH_ASYNC,
+ * ocm_wait, ocm_stream_wait/signal). Out of scope: a max mode, MX-compressed tables,
+ * transfer plans, and scatter-add into remote memory. */
+enum ocm_bag_mode { OCM_BAG_SUM = 0, OCM_BAG_MEAN = 1 };
+struct ocm_bag_params {            /* 104 bytes */
+    uint64_t local_offset;         /* first byte of bag 0's output row, multiple of 16 */
+    uint64_t remote_offset;        /* first byte of remote table row 0, multiple of 16 */
+    uint64_t row_elems;            /* elements per row of both tables */
+    uint64_t bags;                 /* output rows, < 2^32; 0 = empty op */
+    uint64_t ids;                  /* entries of the id array (and of the weights), < 2^32 */
+    uint64_t local_stride;         /* bytes between output rows, multiple of 16 */
+    uint64_t remote_stride;        /* bytes between table rows, multiple of 16 */
+    uint64_t remote_rows;          /* rows the remote table has, < 2^32 */
+    uint64_t index_offset;         /* byte offset IN THE LOCAL HALF of `ids` entries of index_type */
+    uint64_t offsets_offset;       /* same, of bags + 1 entries of index_type */
+    uint64_t weights_offset;       /* same, of `ids` fp32 weights, or OCM_INDEX_NONE */
+    uint32_t index_type;           /* enum ocm_index_type, ids and offsets alike */
+    uint32_t dtype;                /* enum ocm_acc_dtype, both tables alike */
+    uint32_t mode;                 /* enum ocm_bag_mode */
+    uint32_t reserved;             /* must be 0 */
+};
+int ocm_copy_onesided_bag(ocm_alloc_t a, const struct ocm_bag_params *ops, int n_ops, int flags);
 /* One-sided accumulate (the counterpart of MPI_Accumulate): the remote half holds fp32
  * accumulators, the local half elements of `dtype`, and for every element i of every op
  *     remote_f32[i] = remote_f32[i] + scale * widen(local[i]).

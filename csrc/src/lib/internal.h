@@ -10,6 +10,7 @@
 // strided.cpp  strided one-sided ops (ocm_copy_onesided_strided: rows, one stride per side)
 // indexed.cpp  indexed one-sided ops (ocm_copy_onesided_indexed: rows picked by index arrays in the local half)
 // quant_indexed.cpp  indexed converting ops (ocm_copy_onesided_quant_indexed: one MX record per row picked by index arrays)
+// bag.cpp      pooled embedding lookup (ocm_copy_onesided_bag: the rows of every bag summed on the way in)
 // acc.cpp      one-sided accumulate (ocm_copy_onesided_accumulate: remote fp32 += scale * local)
 // libocm.cpp   the C ABI (oncillamem.h)
 // config.cpp   the environment's knobs, parsed once per ocm_init into State::cfg

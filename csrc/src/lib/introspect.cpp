@@ -61,6 +61,17 @@ void ocm_x_quant_indexed_counters(uint64_t out[5]) {
     out[4] = c.bytes_quant_indexed_wire;
 }
 
+// The pooled-lookup counters, likewise: calls, ops, bags named, ids named, nominal bytes read
+// (entries skipped are in ocm_x_indexed_counters' n_indexed_skipped, with the indexed ops').
+void ocm_x_bag_counters(uint64_t out[5]) {
+    const OpCounters &c = S().ctr;
+    out[0] = c.n_bag;
+    out[1] = c.n_bag_ops;
+    out[2] = c.n_bag_bags;
+    out[3] = c.n_bag_ids;
+    out[4] = c.bytes_bag;
+}
+
 // Raw 64-byte handle of extent i (tests: the network tier's capability checks).
 int ocm_x_extent_handle(ocm_alloc_t a, int i, uint8_t *out) {
     if (!a || !out || i < 0 || (size_t)i >= a->ext.size()) return -1;

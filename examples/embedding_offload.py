@@ -21,6 +21,12 @@ trains a second, fp32 table where it lives (oncilla_amd.models.RemoteEmbeddingAd
 a toy regression on looked-up rows, each step ONE fused row-sparse Adam launch, checked against a
 dense torch replay of the same rule on the CPU. The fused step is a GPU kernel: without --gpu the
 library refuses it ("needs a GPU") and --train reports that instead of training some other way.
+
+    python examples/embedding_offload.py --bags 256           # with or without --gpu
+
+pools bags of ids as nn.EmbeddingBag does (RemoteEmbedding.lookup_bags): sum, weighted sum and mean,
+each ONE fused gather-reduce that writes bags x dim sums and no looked-up row, checked against
+torch.nn.functional.embedding_bag within the bound that two summation orders can differ by.
 """
 import argparse
 import os
@@ -83,6 +89,45 @@ def train(c, kind, dev, rows, dim, g, steps=5, batch=1024):
     return True
 
 
+def pooled(c, kind, dev, rows, dim, g, n_bags):
+    """nn.EmbeddingBag's forward over a float32 table in remote memory: n_bags bags of 0 to 40 ids, ONE
+    pooled lookup per call (RemoteEmbedding.lookup_bags), checked against torch's embedding_bag.
+
+    The tolerance, per element of a bag of n entries, with u = 2^-24 and t_i the n terms. Both sides add the
+    same terms in different orders. In any order a term passes through at most n - 1 additions, each within a
+    factor 1 +- u, so a computed sum is within (n - 1) * u * sum|t_i| of the exact one and two computed sums
+    are within 2 * (n - 1) * u * sum|t_i| of each other. A weighted term is fl(w * x) here, two roundings, and
+    may be fused on torch's side: at most one more u on each term, (2 * n - 1) * u in all. Both are within
+        n * 2^-23 * sum|t_i|,
+    the bound for the sum and the weighted sum. The mean is that sum divided by n, once, on either side (torch
+    divides as well: its mean equals its sum / n bit for bit): the sums' bound divided by n, plus one rounding
+    of the quotient on each side, u * (|ours| + |torch's|). sum|t_i| is formed in float64, so that its own
+    rounding does not loosen or tighten the bound."""
+    emb = RemoteEmbedding(c, rows, dim, torch.float32, max_ids=40 * n_bags, kind=kind, stripe_unit=1 << 16, max_bags=n_bags)
+    table = torch.randn((rows, dim), generator=g)
+    emb.load(table.to(dev))
+    lens = torch.randint(0, 41, (n_bags,), generator=g)
+    offsets = torch.cumsum(lens, 0) - lens
+    ids = torch.randint(0, rows, (int(lens.sum()),), generator=g)
+    w = torch.randn(ids.shape, generator=g)
+    bag_of_id = torch.repeat_interleave(torch.arange(n_bags), lens)
+    n = lens.double().unsqueeze(1)
+    for weights, mode in ((None, "sum"), (w, "sum"), (None, "mean")):
+        got = emb.lookup_bags(ids.to(dev), offsets.to(dev), None if weights is None else weights.to(dev), mode=mode)
+        emb.wait()
+        got = got.cpu().double()
+        ref = torch.nn.functional.embedding_bag(ids, table, offsets, mode=mode, per_sample_weights=weights).double()
+        terms = table[ids].double() if weights is None else table[ids].double() * weights.double().unsqueeze(1)
+        mag = torch.zeros(n_bags, dim, dtype=torch.float64).index_add_(0, bag_of_id, terms.abs())  # sum |t_i| per bag element
+        bound = n * 2.0 ** -23 * mag
+        if mode == "mean":
+            bound = bound / n.clamp(min=1) + 2.0 ** -24 * (got.abs() + ref.abs())
+        assert bool(((got - ref).abs() <= bound).all()), f"the pooled lookup ({mode}) left torch's embedding_bag"
+    print(f"--bags: {n_bags} bags ({len(ids)} ids) of a {rows} x {dim} fp32 table in remote memory, one pooled lookup each for "
+          f"sum, weighted sum and mean: equal to embedding_bag within the summation-order bound;", api.bag_counters())
+    emb.close()
+
+
 def roundtrip(rows, fmt):
     """What a compressed table gives back for `rows`: the oracle decode of their oracle encode (no format: the rows)."""
     if fmt is None:
@@ -99,6 +144,7 @@ def main():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--compress", choices=["mxfp8", "mxfp4"], default=None, help="keep the table as MX records, one per row")
     ap.add_argument("--train", action="store_true", help="also train a table in place with the fused row-sparse Adam")
+    ap.add_argument("--bags", type=int, default=0, metavar="N", help="also pool N bags of ids with one fused gather-reduce per call")
     args = ap.parse_args()
     if args.gpu is None:
         os.environ["OCM_NO_GPU"] = "1"
@@ -146,6 +192,8 @@ def main():
             emb.close()
             if args.train:
                 train(c, kind, dev, args.rows, args.dim, g)
+            if args.bags:
+                pooled(c, kind, dev, args.rows, args.dim, g, args.bags)
 
 
 if __name__ == "__main__":

@@ -143,6 +143,31 @@ class OcmQuantIndexedParams(ctypes.Structure):
 assert ctypes.sizeof(OcmQuantIndexedParams) == 96
 
 
+class OcmBagParams(ctypes.Structure):
+    """struct ocm_bag_params (104 bytes)."""
+
+    _fields_ = [
+        ("local_offset", ctypes.c_uint64),
+        ("remote_offset", ctypes.c_uint64),
+        ("row_elems", ctypes.c_uint64),
+        ("bags", ctypes.c_uint64),
+        ("ids", ctypes.c_uint64),
+        ("local_stride", ctypes.c_uint64),
+        ("remote_stride", ctypes.c_uint64),
+        ("remote_rows", ctypes.c_uint64),
+        ("index_offset", ctypes.c_uint64),
+        ("offsets_offset", ctypes.c_uint64),
+        ("weights_offset", ctypes.c_uint64),
+        ("index_type", ctypes.c_uint32),
+        ("dtype", ctypes.c_uint32),
+        ("mode", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(OcmBagParams) == 104
+
+
 class OcmAdamRows(ctypes.Structure):
     """struct ocm_adam_rows (csrc/include/ocm/adam_rows.h): the descriptor of one row-sparse Adam step."""
     _fields_ = [
@@ -288,6 +313,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_copy_onesided_strided": (i32, [vp, ctypes.POINTER(OcmStridedParams), i32, i32]),
             "ocm_copy_onesided_indexed": (i32, [vp, ctypes.POINTER(OcmIndexedParams), i32, i32]),
             "ocm_copy_onesided_quant_indexed": (i32, [vp, ctypes.POINTER(OcmQuantIndexedParams), i32, i32]),
+            "ocm_copy_onesided_bag": (i32, [vp, ctypes.POINTER(OcmBagParams), i32, i32]),
             "ocm_copy_onesided_accumulate": (i32, [vp, ctypes.POINTER(OcmAccParams), i32, i32]),
             "ocm_stream_wait": (i32, [vp, vp]),
             "ocm_plan_create": (vp, []),
@@ -316,6 +342,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
             "ocm_x_quant_strided_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_indexed_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_quant_indexed_counters": (None, [ctypes.POINTER(u64)]),
+            "ocm_x_bag_counters": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_stats": (None, [ctypes.POINTER(u64)]),
             "ocm_x_service_health": (None, [ctypes.POINTER(u64)]),
             "ocm_x_tick_stats": (ctypes.c_int, [ctypes.POINTER(u64)]),
@@ -414,6 +441,9 @@ OCM_INDEX_I64 = 2
 INDEXED_COUNTER_KEYS = ["n_indexed", "n_indexed_ops", "n_indexed_rows", "bytes_indexed", "n_indexed_skipped"]
 QUANT_INDEXED_COUNTER_KEYS = ["n_quant_indexed", "n_quant_indexed_ops", "n_quant_indexed_rows", "bytes_quant_indexed_src",
                               "bytes_quant_indexed_wire"]
+OCM_BAG_SUM = 0  # enum ocm_bag_mode
+OCM_BAG_MEAN = 1
+BAG_COUNTER_KEYS = ["n_bag", "n_bag_ops", "n_bag_bags", "n_bag_ids", "bytes_bag"]
 
 
 class Plan:
@@ -651,6 +681,55 @@ def quant_indexed_ops(ops, dtype, index_type=OCM_INDEX_I64, format="mxfp8") -> B
     b.keep = rec
     b.quant_indexed = True
     return b
+
+
+def bag_mode(mode) -> int:
+    """enum ocm_bag_mode of "sum" / "mean", or of the enum value itself. There is no "max"."""
+    if isinstance(mode, int):
+        return mode
+    try:
+        return {"sum": OCM_BAG_SUM, "mean": OCM_BAG_MEAN}[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"pooled lookups take the mode 'sum' or 'mean', not {mode!r}") from None
+
+
+def bag_ops(ops, dtype, index_type=OCM_INDEX_I64, mode="sum") -> BatchOps:
+    """Descriptor list for Allocation.bag_batch from an (n, 11) integer array (or rows)
+    [local_offset, remote_offset, row_elems, bags, ids, local_stride, remote_stride, remote_rows,
+    index_offset, offsets_offset, weights_offset], the fields of struct ocm_bag_params in order,
+    every op with `dtype` (see :func:`acc_dtype`) and `index_type` (see :func:`index_type_of`),
+    built once (no per-op Python objects). An op without weights has OCM_INDEX_NONE (or -1) as its
+    weights_offset. mode: "sum" or "mean" for every op, or a sequence with one of them per op."""
+    import numpy as np
+
+    if isinstance(ops, np.ndarray) and ops.dtype.kind in "iu":
+        a = ops.astype(np.uint64).reshape(-1, 11)  # -1 wraps to OCM_INDEX_NONE
+    else:  # Python integers: OCM_INDEX_NONE fits no int64
+        flat = np.array(ops, dtype=object).reshape(-1)
+        a = np.array([int(v) & OCM_INDEX_NONE for v in flat], dtype=np.uint64).reshape(-1, 11)
+    n = int(a.shape[0])
+    names = ("lo", "ro", "re", "bags", "ids", "ls", "rs", "rr", "io", "oo", "wo")
+    rec = np.zeros(max(1, n), dtype=np.dtype([(name, "<u8") for name in names] +
+                                             [("it", "<u4"), ("dt", "<u4"), ("mode", "<u4"), ("rsv", "<u4")]))
+    if n:
+        for col, name in enumerate(names):
+            rec[name][:n] = a[:, col]
+        rec["it"][:n] = index_type_of(index_type)
+        rec["dt"][:n] = acc_dtype(dtype)
+        rec["mode"][:n] = bag_mode(mode) if isinstance(mode, (str, int)) else np.array([bag_mode(m) for m in mode], dtype=np.uint32)
+    b = BatchOps(rec.ctypes.data_as(ctypes.POINTER(OcmBagParams)), n)
+    b.keep = rec
+    b.bag = True
+    return b
+
+
+def bag_counters() -> dict:
+    """This process's pooled-lookup counters (ocm_x_bag_counters): calls, ops, bags and ids named by
+    the non-empty ops, and the nominal bytes read (ids * row bytes). The entries they skip are counted
+    in indexed_counters()["n_indexed_skipped"]."""
+    out = (ctypes.c_uint64 * len(BAG_COUNTER_KEYS))()
+    load().ocm_x_bag_counters(out)
+    return dict(zip(BAG_COUNTER_KEYS, [int(v) for v in out]))
 
 
 def quant_indexed_counters() -> dict:
@@ -1206,6 +1285,22 @@ class Allocation:
         if self._c.lib.ocm_copy_onesided_quant_indexed(self.handle, arr.array, arr.n,
                                                        OCM_BATCH_ASYNC if async_ else 0) != 0:
             raise OcmError("ocm_copy_onesided_quant_indexed: " + last_error())
+
+    def bag_batch(self, ops, dtype=None, index_type=OCM_INDEX_I64, mode="sum", async_: bool = False) -> None:
+        """Pooled lookups in one launch (ocm_copy_onesided_bag, a get only): bag b of an op is the
+        ids [off[b], off[b + 1]) of its id array, and output row b becomes the sum (the weighted sum
+        with per-id fp32 weights, or the mean) of the remote table rows those ids pick, added in order
+        in fp32 with two roundings per term and narrowed to `dtype` once; an empty bag gives zeros. The
+        ids, the bags + 1 offsets and the weights live in the LOCAL half and are read when the transfer
+        runs. Ids outside the table add nothing and are counted: a blocking call then raises OcmError
+        naming their number after writing every bag, an async one makes the next wait() raise it, as
+        for indexed_batch. ops: an (n, 11) array or rows for :func:`bag_ops` with `dtype`, `index_type`
+        and `mode`, or a prepared bag_ops list."""
+        arr = ops if isinstance(ops, BatchOps) else bag_ops(ops, dtype, index_type, mode)
+        if not getattr(arr, "bag", False):
+            raise TypeError("bag_batch takes a bag_ops list, not a batch_ops, quant_ops, strided_ops, indexed_ops or acc_ops one")
+        if self._c.lib.ocm_copy_onesided_bag(self.handle, arr.array, arr.n, OCM_BATCH_ASYNC if async_ else 0) != 0:
+            raise OcmError("ocm_copy_onesided_bag: " + last_error())
 
     def strided_batch(self, ops, async_: bool = False) -> None:
         """Strided one-sided ops in one launch (ocm_copy_onesided_strided): row r of an op moves

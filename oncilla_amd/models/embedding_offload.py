@@ -23,6 +23,13 @@ Ids outside [0, num_rows) move nothing: their output rows keep what they held, t
 counted, and IndexError names the count, at once for a blocking lookup and at ``wait()``
 for an async one.
 
+``max_bags > 0`` adds what nn.EmbeddingBag's forward needs: ``lookup_bags(ids, offsets)`` runs
+ONE pooled lookup (ocm_copy_onesided_bag) that reads every bag's rows out of the remote half,
+sums them in registers (in order, in fp32; optionally weighted, or the mean) and writes
+``bags x dim`` sums. No row is written to the local half and read back, the output region
+is sized for the bags of a batch and not for its ids, and there is no second launch. Ids
+outside the table add nothing to their bag and are reported as above.
+
 RemoteEmbeddingAdam trains such a table where it lives: one fused row-sparse Adam launch per
 step (ocm_x_adam_rows) on the rows whose ids were in the batch, with the moments (and, for a
 bfloat16 table, fp32 master rows) in the remote half of a second pair.
@@ -40,11 +47,13 @@ class RemoteEmbedding:
     """num_rows x dim table of `dtype` in a remote half; lookups of up to max_ids ids. compress:
     None, or "mxfp8" / "mxfp4" for a table of float16 or bfloat16 rows with dim % 32 == 0 kept as
     one MX record per row. record_stride: bytes from one row to the next in the remote half;
-    remote_bytes: the bytes the table takes there."""
+    remote_bytes: the bytes the table takes there. max_bags: 0, or the most bags one lookup_bags
+    call pools (a table of float32, bfloat16 or float16 rows of a multiple of 16 bytes); with 0 the
+    local half is laid out as it always was."""
 
     def __init__(self, client: api.Client, num_rows: int, dim: int, dtype=None, max_ids: int = 4096,
                  kind: int = api.OCM_REMOTE_GPU, flags: int = api.OCM_ALLOC_STRIPE, stripe_unit: int = 0,
-                 remote_rank: int = -1, compress=None):
+                 remote_rank: int = -1, compress=None, max_bags: int = 0):
         import torch
 
         self.dtype = dtype or torch.float16
@@ -67,7 +76,20 @@ class RemoteEmbedding:
         self.remote_bytes = self.num_rows * self.record_stride
         out_bytes = self.max_ids * self.row_bytes
         self._ids_off = (out_bytes + 15) // 16 * 16  # int64 ids, or int32 in the same region
-        self.alloc = client.alloc(kind, local_bytes=self._ids_off + 8 * self.max_ids,
+        local_bytes = self._ids_off + 8 * self.max_ids
+        self.max_bags = int(max_bags)
+        if self.max_bags < 0:
+            raise ValueError("max_bags must not be negative")
+        if self.max_bags:
+            if compress is None and (self.row_bytes % 16 != 0 or self.dtype not in (torch.float32, torch.bfloat16, torch.float16)):
+                raise ValueError(f"pooled lookups need float32, bfloat16 or float16 rows of a multiple of 16 bytes, "
+                                 f"not {self.dim} x {self.dtype}")
+            # behind the ids: bags + 1 offsets (typed as the ids are), one fp32 weight per id, the bags' sums
+            self._offs_off = local_bytes
+            self._w_off = self._offs_off + 8 * (self.max_bags + 1)
+            self._bag_off = (self._w_off + 4 * self.max_ids + 15) // 16 * 16
+            local_bytes = self._bag_off + self.max_bags * self.row_bytes
+        self.alloc = client.alloc(kind, local_bytes=local_bytes,
                                   remote_bytes=self.remote_bytes, remote_rank=remote_rank, flags=flags,
                                   stripe_unit=stripe_unit)
         raw = self.alloc.local_tensor(torch.uint8)
@@ -75,6 +97,12 @@ class RemoteEmbedding:
         self.out = raw[:out_bytes].view(self.dtype).view(self.max_ids, self.dim)
         self._ids = {torch.int64: raw[self._ids_off: self._ids_off + 8 * self.max_ids].view(torch.int64),
                      torch.int32: raw[self._ids_off: self._ids_off + 4 * self.max_ids].view(torch.int32)}
+        if self.max_bags:
+            n = self.max_bags + 1
+            self._offs = {torch.int64: raw[self._offs_off: self._offs_off + 8 * n].view(torch.int64),
+                          torch.int32: raw[self._offs_off: self._offs_off + 4 * n].view(torch.int32)}
+            self._w = raw[self._w_off: self._w_off + 4 * self.max_ids].view(torch.float32)
+            self.bag_out = raw[self._bag_off: self._bag_off + self.max_bags * self.row_bytes].view(self.dtype).view(self.max_bags, self.dim)
 
     def load(self, weight) -> None:
         """Put the whole table (num_rows x dim, any device), in chunks staged through the output region."""
@@ -126,6 +154,52 @@ class RemoteEmbedding:
         if k:
             self._run(False, k, itype, async_)
         return self.out[:k]
+
+    def lookup_bags(self, ids, offsets, per_sample_weights=None, mode: str = "sum", async_: bool = True):
+        """nn.functional.embedding_bag's forward over the remote table: bag b is ids[offsets[b]:
+        offsets[b + 1]] (the last one runs to the end of ids, as torch's does), and row b of the result
+        is the sum of the table rows its ids pick, their weighted sum with per_sample_weights (one per
+        id, mode "sum" only), or their mean. A (bags, dim) view of the bag-output region, valid until
+        the next lookup_bags. The terms are added in the order of ids, in fp32, and the sum is narrowed to
+        the table's dtype once: torch adds in another order, so the two agree to rounding, not bit for
+        bit. offsets gets its closing entry len(ids) on the device; nothing syncs the host. Streams and
+        ids outside the table (IndexError; they add nothing to their bag) as for lookup."""
+        import torch
+
+        if self.compress is not None:
+            raise TypeError(f"lookup_bags does not serve a compressed ({self.compress}) table: pooling MX records is not built")
+        if not self.max_bags:
+            raise ValueError("lookup_bags needs a RemoteEmbedding made with max_bags > 0")
+        if per_sample_weights is not None and mode != "sum":
+            raise ValueError("per_sample_weights go with mode 'sum' only")
+        bags = int(offsets.numel())
+        if bags > self.max_bags:
+            raise ValueError(f"{bags} bags in one call, the bag-output region holds {self.max_bags}")
+        if offsets.dtype not in self._offs:
+            raise TypeError(f"offsets must be int32 or int64, not {offsets.dtype}")
+        k, itype = self._stage_ids(ids)
+        if per_sample_weights is not None and int(per_sample_weights.numel()) != k:
+            raise ValueError(f"{int(per_sample_weights.numel())} weights for {k} ids")
+        if bags == 0:
+            return self.bag_out[:0]
+        # on torch's current stream, as the ids are: the offsets in the ids' type, then the closing entry
+        offs = self._offs[ids.dtype]
+        offs[:bags].copy_(offsets.reshape(-1), non_blocking=True)
+        offs[bags:bags + 1].fill_(k)
+        w_off = api.OCM_INDEX_NONE
+        if per_sample_weights is not None and k:
+            self._w[:k].copy_(per_sample_weights.reshape(-1), non_blocking=True)
+            w_off = self._w_off
+        op = [[self._bag_off, 0, self.dim, bags, k, self.row_bytes, self.record_stride, self.num_rows, self._ids_off,
+               self._offs_off, w_off]]
+        self.alloc.stream_wait()  # after the copies above, and the kernels that produced what they copied
+        try:
+            self.alloc.bag_batch(api.bag_ops(op, self.dtype, itype, mode), async_=async_)
+        except api.OcmError as e:
+            raise _index_error(e) from None
+        if async_:
+            self.alloc.stream_signal()  # torch's stream reads the sums after the lookup
+        return self.bag_out[:bags]
 
     def update(self, ids, rows, async_: bool = False) -> None:
         """Scatter put: table row ids[i] = rows[i]. The ids must be unique: two rows for one id have
@@ -238,6 +312,28 @@ class RemoteEmbeddingAdam:
         emb.alloc.adam_rows(self.state, uniq, g, (0, emb.row_bytes), (self.off["m"], rb), (self.off["v"], rb),
                             self._hp(self.t), emb.num_rows, master=(self.off["w"], rb) if self.bf16 else None,
                             gscale=scale, skipped=self._skipped)
+
+    def step_bags(self, ids, offsets, grad_bags, per_sample_weights=None, scale: float = 1.0) -> None:
+        """One step from the gradient of a lookup_bags(ids, offsets, per_sample_weights) sum: the
+        gradient of the row an id picked is its bag's gradient row (times the id's weight). The bag
+        gradient (bags x dim) is expanded to one row per id with torch on the device, in fp32, and
+        handed to ``step``: there is no kernel of its own."""
+        import torch
+
+        ids = ids.reshape(-1)
+        k, bags = int(ids.numel()), int(offsets.numel())
+        if tuple(grad_bags.shape) != (bags, self.emb.dim):
+            raise ValueError(f"grad_bags must be {bags} x {self.emb.dim}")
+        if per_sample_weights is not None and int(per_sample_weights.numel()) != k:
+            raise ValueError(f"{int(per_sample_weights.numel())} weights for {k} ids")
+        offs = offsets.reshape(-1).to(device=ids.device, dtype=torch.int64)
+        ends = torch.cat([offs[1:], torch.full((1,), k, dtype=torch.int64, device=ids.device)])
+        # output_size: the host already knows it, so repeat_interleave does not sync for it
+        bag_of_id = torch.repeat_interleave(torch.arange(bags, device=ids.device), ends - offs, output_size=k)
+        g = grad_bags.float().index_select(0, bag_of_id)
+        if per_sample_weights is not None:
+            g = g * per_sample_weights.reshape(-1).float().unsqueeze(1)
+        self.step(ids, g, scale)
 
     def skipped(self) -> int:
         """Rows skipped so far because their id was outside the table. A host sync; resets nothing."""
